@@ -13,7 +13,16 @@ Inputs are generated in HBM by the counter-based splitmix64 generators before ti
 ranks come from RANK / LOCAL_RANK / WORLD_SIZE. N > 1 runs on RCCL (nccl); `--dist-backend gloo
 --device-override 0` rehearses N ranks on one GPU.
 
-The same JSON line carries `secondary` measurements of the other BASELINE workloads, each timed the
+A plain run does only that: it builds the shard, warms up, times the --steps steps, writes the last step's outputs
+when `--dump-outputs DIR` is given and prints the result line. Everything else the benchmark measures (the
+`secondary` workloads below and the CPU baselines) runs only with `--full`.
+
+`--dump-outputs DIR` writes what the last timed step returned, the folded states of the suite's ops, as float64
+arrays: DIR/states.npy (one row per op: the state's fields in dq_state order, zero-padded), DIR/metrics.npy (each
+op's metric value) and DIR/present.npy (1 where the op has a state, else 0 and zeros in the other two). The inputs are
+counter-based, so the same arguments give the same arrays on every run.
+
+With `--full` the same JSON line carries `secondary` measurements of the other BASELINE workloads, each timed the
 same way (its own steps, HIP events on the scan stream, its own roofline):
   suite10  the north-star 10-analyzer suite over the same 8 columns (C2 ops + Compliance(c > 0) +
            ApproxCountDistinct + Correlation(c_2k, c_2k+1): 69 ops), every rank count;
@@ -24,7 +33,10 @@ same way (its own steps, HIP events on the scan stream, its own roofline):
   c2_host_streamed  the C2 suite over pinned host columns streamed through HBM (dq_scan_streamed): the
            end-to-end rate including the host link, never the headline value (N = 1).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--scaling weak|strong] [--no-secondary]
+`--full` also adds `cpu_baseline` legs (`--no-cpu` leaves them out, `--no-secondary` the secondary workloads).
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--scaling weak|strong] [--dump-outputs DIR]
+                    [--full [--no-secondary] [--no-cpu]]
 """
 import argparse
 import ctypes
@@ -695,6 +707,41 @@ def measured_traffic(rows_per_gpu):
     return (found[0]["traffic_bytes_per_call"] / 1e9, found[1]) if found else None
 
 
+def dump_outputs(dirname, N, states, state_from_native):
+    """--dump-outputs: the folded states the last timed step returned (one dq_state per op of the suite) as
+    DIR/states.npy, float64 [ops, 3] (the state's fields in dq_state order, 0 where it has fewer or is absent),
+    DIR/metrics.npy, float64 [ops] (the metric each state yields, 0 for an absent state) and DIR/present.npy, float64
+    [ops] (1 where the op has a state and a metric, else 0). Every written value is finite for finite inputs."""
+    fields = np.zeros((len(states), 3), dtype=np.float64)
+    metrics = np.zeros(len(states), dtype=np.float64)
+    present = np.zeros(len(states), dtype=np.float64)
+    for i, st in enumerate(states):
+        if not st.present:
+            continue
+        k, u = st.kind, st.u
+        if k == N.OP_SIZE:
+            row = [u.num_matches.num_matches]
+        elif k in (N.OP_COMPLETENESS, N.OP_COMPLIANCE):
+            row = [u.num_matches_and_count.num_matches, u.num_matches_and_count.count]
+        elif k == N.OP_MEAN:
+            row = [u.mean.sum, u.mean.count]
+        elif k in (N.OP_SUM, N.OP_MINIMUM, N.OP_MAXIMUM):
+            row = [u.dbl.value]
+        elif k == N.OP_STANDARD_DEVIATION:
+            row = [u.stddev.n, u.stddev.avg, u.stddev.m2]
+        else:
+            raise ValueError("dump_outputs: no layout for state kind %d" % k)
+        state = state_from_native(st)
+        if state is not None:
+            fields[i, :len(row)] = row
+            metrics[i] = state.metricValue()
+            present[i] = 1.0
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "states.npy"), fields)
+    np.save(os.path.join(dirname, "metrics.npy"), metrics)
+    np.save(os.path.join(dirname, "present.npy"), present)
+
+
 def spawn_ranks(args):
     """`--gpus N` without a launcher: start N rank processes of this script (RANK / LOCAL_RANK / WORLD_SIZE /
     MASTER_* set, rendezvous on 127.0.0.1), forward rank 0's stdout, and return the first failing exit status. The
@@ -764,8 +811,13 @@ def main():
     ap.add_argument("--rows", type=float, default=1e9)
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-sample-rows", type=int, default=8_000_000)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="only the headline C2 line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run, also the secondary workloads and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's folded states as DIR/states.npy, DIR/metrics.npy and "
+                         "DIR/present.npy (float64)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: only the headline C2 line")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (RCCL over xGMI) or gloo (rehearsal on one GPU)")
     ap.add_argument("--device-override", type=int, default=None, help="run every rank on this GPU (rehearsal)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="strong",
@@ -821,6 +873,8 @@ def main():
     # sanity: the folded Size equals the table size
     size_state = state_from_native(states[c2.offsets[0][0]])
     assert size_state.numMatches == total, (size_state, total)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, N, states, state_from_native)
 
     alg_bytes = bytes_per_row * nrows
     achieved = alg_bytes / (scan_ms * 1e-3) / 1e9
@@ -855,7 +909,7 @@ def main():
                                % (scan_ms, args.steps, bytes_per_row, nrows)},
     }
     del c2
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         sec = {}
         s10 = ScanWorkload(torch, N, D, ctx, table, suite10_analyzers(D, names), stream, dev, world, args.dist_backend)
         el, kms, st = timed(torch, dist, world, max(3, args.steps // 4), 1, stream, s10.step)
@@ -931,7 +985,7 @@ def main():
             sec["c5_shard"] = bench_c5(torch, N, D, ctx, dev, min(total, 250_000_000), 2)
             torch.cuda.empty_cache()
         result["secondary"] = sec
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         result["cpu_baseline"] = cpu_baseline(args.cpu_seconds, args.cpu_sample_rows)
         if "secondary" in result:
             sec = result["secondary"]

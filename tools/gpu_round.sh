@@ -13,10 +13,14 @@ if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 timeout -k 10 180 python -u -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${TAG}_smoke.log 2>&1
 rc=$?; echo "smoke rc=$rc"; tail -3 gpurun_out/${TAG}_smoke.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
-timeout -k 10 300 python -u bench.py --rows $ROWS --steps 20 --warmup 3 --cpu-seconds 10 > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
-rc=$?; echo "bench rc=$rc"; cat gpurun_out/${TAG}_bench.json; tail -5 gpurun_out/${TAG}_bench.err
+# the bench line with its secondary workloads and CPU baselines (--full), then the same under a kernel trace
+OUT="$PWD/${BENCH_OUT:-bench_out}"
+mkdir -p "$OUT"
+timeout -k 10 600 python -u bench.py --full --rows $ROWS --steps 20 --warmup 3 --cpu-seconds 10 > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
+rc=$?; echo "bench rc=$rc"; cat "$OUT/${TAG}_bench.json"; tail -5 "$OUT/${TAG}_bench.err"
 if [ $rc -ne 0 ]; then exit $rc; fi
-cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "${GRAFT_REPO_ROOT:-/root/repo}/gpurun_out/${TAG}_prof" -o run --output-format csv -- python3 "${GRAFT_REPO_ROOT:-/root/repo}/bench.py" --rows $ROWS --steps 10 --warmup 2 --no-cpu > "${GRAFT_REPO_ROOT:-/root/repo}/gpurun_out/${TAG}_prof_bench.json" 2>&1
+BENCH="$PWD/bench.py"
+cd "$TMPDIR" && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/${TAG}_prof" -o run --output-format csv -- python3 "$BENCH" --full --rows $ROWS --steps 10 --warmup 2 --no-cpu > "$OUT/${TAG}_prof_bench.json" 2>&1
 rc=$?; echo "rocprof rc=$rc"
-find "${GRAFT_REPO_ROOT:-/root/repo}/gpurun_out/${TAG}_prof" -name "*stats*" | head
+find "$OUT/${TAG}_prof" -name "*stats*" | head
 exit $rc
