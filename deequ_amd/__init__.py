@@ -24,6 +24,7 @@ from .table import ChunkedTable, Table, Column
 from .profiles import (ColumnProfiler, ColumnProfilerRunner, ColumnProfilerRunBuilder, ColumnProfiles,
                        StandardColumnProfile, NumericColumnProfile, DataTypeInstances)
 from .state_provider import HdfsStateProvider, FileSystemStateProvider
+from .schema import (RowLevelSchema, RowLevelSchemaValidator, RowLevelSchemaValidationResult)
 from . import distributed
 
 __all__ = [n for n in dir() if not n.startswith("_")]

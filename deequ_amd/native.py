@@ -71,6 +71,8 @@ EXPORTED_SYMBOLS = (
     "dq_freq_mutual_information", "dq_open_devices", "dq_ctx_num_devices", "dq_ctx_uses_rccl", "dq_scan_sharded",
     "dq_scan_streamed", "dq_scan_kernel_launches", "dq_freq_path_count", "dq_kll_sketch_columns",
     "dq_kll_merge_states", "dq_scratch_trim", "dq_frequencies_parts", "dq_set_priority",
+    "dq_schema_validate", "dq_schema_launch_count", "dq_gather_rows", "dq_parse_int32", "dq_parse_decimal",
+    "dq_parse_timestamp",
 )
 
 
@@ -179,6 +181,23 @@ class DqFreqOptions(ctypes.Structure):
 
 STATE_SIZE = ctypes.sizeof(DqState)
 
+SCHEMA_STRING, SCHEMA_INT, SCHEMA_DECIMAL, SCHEMA_TIMESTAMP = 1, 2, 3, 4
+SCHEMA_AMBIGUOUS_NULL = 0x1
+PARSE_NULL, PARSE_VALUE, PARSE_AMBIGUOUS = 0, 1, 2
+
+
+class DqSchemaColumn(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("column", ctypes.c_int32), ("nullable", ctypes.c_int32),
+                ("has_min", ctypes.c_int32), ("has_max", ctypes.c_int32), ("precision", ctypes.c_int32),
+                ("scale", ctypes.c_int32), ("program_len", ctypes.c_int32), ("min_value", ctypes.c_int64),
+                ("max_value", ctypes.c_int64), ("program", ctypes.c_void_p), ("cast_values", ctypes.c_void_p),
+                ("cast_validity", ctypes.c_void_p)]
+
+
+class DqSchemaResult(ctypes.Structure):
+    _fields_ = [("num_valid", ctypes.c_int64), ("num_invalid", ctypes.c_int64), ("num_unknown", ctypes.c_int64),
+                ("num_ambiguous", ctypes.c_int64), ("first_ambiguous_column", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
 
 class NativeError(RuntimeError):
     """A failed libdq call (status code + dq_last_error message)."""
@@ -258,6 +277,15 @@ def load_library(path=None):
             "dq_ctx_uses_rccl": (c_int, [c_void_p]),
             "dq_scan_sharded": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                                         c_void_p]),
+            "dq_schema_validate": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_uint32, c_void_p,
+                                           c_void_p, c_void_p, c_void_p]),
+            "dq_schema_launch_count": (c_int64, [c_void_p]),
+            "dq_gather_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]),
+            "dq_parse_int32": (c_int, [ctypes.c_char_p, ctypes.c_int32, c_void_p]),
+            "dq_parse_decimal": (c_int, [ctypes.c_char_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_void_p]),
+            "dq_parse_timestamp": (c_int, [ctypes.c_char_p, ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32,
+                                           c_void_p]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name)
@@ -273,6 +301,27 @@ def hll_count(words):
     lib = load_library()
     arr = (ctypes.c_int64 * HLL_NUM_WORDS)(*[int(np.int64(np.uint64(w & 0xFFFFFFFFFFFFFFFF))) for w in words])
     return lib.dq_hll_count(arr)
+
+
+def parse_int32(cell):
+    """dq_parse_int32: cast(cell as int) of the row-level schema validator, (class, value) (host-side, C-ABI)."""
+    out = ctypes.c_int32(0)
+    rc = load_library().dq_parse_int32(cell, len(cell), ctypes.byref(out))
+    return rc, (int(out.value) if rc == PARSE_VALUE else None)
+
+
+def parse_decimal(cell, precision, scale):
+    """dq_parse_decimal: cast(cell as decimal(precision, scale)), (class, unscaled value)."""
+    out = ctypes.c_int64(0)
+    rc = load_library().dq_parse_decimal(cell, len(cell), int(precision), int(scale), ctypes.byref(out))
+    return rc, (int(out.value) if rc == PARSE_VALUE else None)
+
+
+def parse_timestamp(program, cell):
+    """dq_parse_timestamp: unix_timestamp(cell, mask) over a compiled mask, (class, microseconds)."""
+    out = ctypes.c_int64(0)
+    rc = load_library().dq_parse_timestamp(program, len(program), cell, len(cell), ctypes.byref(out))
+    return rc, (int(out.value) if rc == PARSE_VALUE else None)
 
 
 def kll_merge_states(a, b):
@@ -502,6 +551,32 @@ class Context:
         self.check(self.lib.dq_cast_column(self.handle, ctypes.byref(column), int(nrows), int(to_type),
                                             ctypes.c_void_p(values_dev_ptr), ctypes.c_void_p(validity_dev_ptr)),
                    "dq_cast_column")
+
+    def schema_launch_count(self):
+        return int(self.lib.dq_schema_launch_count(self.handle))
+
+    def schema_validate(self, columns, nrows, defs, flags, true_ptr, false_ptr, ambiguous_ptr):
+        """dq_schema_validate: returns (status, DqSchemaResult); a failed call is left to the caller, which names the
+        ambiguous column from the result."""
+        self._after_torch_stream()
+        col_arr = (DqColumn * max(len(columns), 1))(*columns)
+        def_arr = (DqSchemaColumn * max(len(defs), 1))(*defs)
+        res = DqSchemaResult()
+        rc = self.lib.dq_schema_validate(self.handle, col_arr, len(columns), int(nrows), def_arr, len(defs), int(flags),
+                                         ctypes.c_void_p(true_ptr), ctypes.c_void_p(false_ptr),
+                                         ctypes.c_void_p(ambiguous_ptr), ctypes.byref(res))
+        return rc, res
+
+    def gather_rows(self, column, nrows, select_ptr, nselected, values_ptr, validity_ptr, offsets_ptr=None):
+        """dq_gather_rows; returns the bytes of a string gather."""
+        self._after_torch_stream()
+        nbytes = ctypes.c_int64(0)
+        self.check(self.lib.dq_gather_rows(self.handle, ctypes.byref(column), int(nrows), ctypes.c_void_p(select_ptr),
+                                           int(nselected), ctypes.c_void_p(values_ptr) if values_ptr else None,
+                                           ctypes.c_void_p(validity_ptr) if validity_ptr else None,
+                                           ctypes.c_void_p(offsets_ptr) if offsets_ptr else None, ctypes.byref(nbytes)),
+                   "dq_gather_rows")
+        return int(nbytes.value)
 
     def _after_torch_stream(self):
         """The generators run on the context's stream; a buffer torch just allocated and filled (torch.zeros) on its

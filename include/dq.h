@@ -471,6 +471,73 @@ int64_t dq_kll_merge_states(const uint8_t* a, int64_t na, const uint8_t* b, int6
 int dq_cast_column(dq_ctx* ctx, const dq_column* column, int64_t nrows, int32_t to_type, void* values_dev,
                    uint8_t* validity_dev);
 
+/* ---------------------------------------------------------------------------------------------
+ * Row-level schema validation (schema/RowLevelSchemaValidator.scala:183-281): one fused verdict
+ * pass over STRING columns, then a row compaction. Single-device contexts, device-resident columns.
+ * ------------------------------------------------------------------------------------------- */
+typedef enum dq_schema_kind {
+    DQ_SCHEMA_STRING = 1,    /* min / max: UTF-8 character counts; program: a regex image (deequ_amd/regex.py) */
+    DQ_SCHEMA_INT = 2,       /* cast(c as int); min / max: value bounds (int32 range)                          */
+    DQ_SCHEMA_DECIMAL = 3,   /* cast(c as decimal(precision, scale)), 0 <= scale <= precision <= 18            */
+    DQ_SCHEMA_TIMESTAMP = 4  /* unix_timestamp(c, mask); program: the compiled mask (see below)               */
+} dq_schema_kind;
+
+/* One column definition. `program` is host memory: for STRING the compiled regex (program_len 0 = no `matches`), for
+ * TIMESTAMP the mask as a byte program of elements {0, b} = the literal byte b and {1..6} = the fields yyyy MM dd HH
+ * mm ss (each at most once, never two in a row). cast_values / cast_validity (INT: nrows x int32, DECIMAL: nrows x
+ * int64 unscaled, TIMESTAMP: nrows x int64 microseconds UTC; validity ceil(nrows / 64) x 8 B) are device buffers,
+ * 8-B aligned, written for every row (NULL where the cell is NULL or does not cast); either may be NULL. */
+typedef struct dq_schema_column {
+    int32_t kind;              /* dq_schema_kind                                  */
+    int32_t column;            /* index into `columns`: a STRING column           */
+    int32_t nullable;          /* 0 adds the clause `c IS NOT NULL`               */
+    int32_t has_min, has_max;
+    int32_t precision, scale;  /* DECIMAL                                         */
+    int32_t program_len;       /* bytes                                           */
+    int64_t min_value, max_value;
+    const void* program;
+    void* cast_values;
+    uint8_t* cast_validity;
+} dq_schema_column;
+
+typedef struct dq_schema_result {
+    int64_t num_valid;               /* rows whose verdict is TRUE                                          */
+    int64_t num_invalid;             /* FALSE                                                               */
+    int64_t num_unknown;             /* NULL: a NULL cell of an INT column with a minimum (reference :246)  */
+    int64_t num_ambiguous;           /* rows with a cell whose JVM parse this engine does not reproduce     */
+    int32_t first_ambiguous_column;  /* `column` of the first definition with such a cell, or -1            */
+    int32_t pad;
+} dq_schema_result;
+
+#define DQ_SCHEMA_AMBIGUOUS_NULL 0x1u /* an ambiguous cell casts to NULL (default: the call fails) */
+
+/* The verdict of every row under `defs` (SQL three-valued AND of the reference's CNF clauses, in definition order) in
+ * one kernel launch, with the casts of the INT / DECIMAL / TIMESTAMP definitions. true_bits / false_bits /
+ * ambiguous_bits: device bitmaps of ceil(nrows / 64) x 8 B (LSB-first), any may be NULL (counts only). String bytes
+ * buffers are 4-B aligned with >= 16 readable bytes past the end. Ambiguous cells (a byte >= 0x80 in a DECIMAL /
+ * TIMESTAMP cell, a decimal exponent past +-10000, a timestamp that SimpleDateFormat's lenient parse may accept but
+ * is not exactly the mask's shape with in-range fields) fail the call with DQ_ERR_UNSUPPORTED — `result` is filled
+ * — unless flags has DQ_SCHEMA_AMBIGUOUS_NULL. */
+int dq_schema_validate(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, const dq_schema_column* defs,
+                       int ndefs, uint32_t flags, uint8_t* true_bits, uint8_t* false_bits, uint8_t* ambiguous_bits,
+                       dq_schema_result* result);
+/* Verdict-kernel launches of this context so far (one per call with rows and definitions). */
+int64_t dq_schema_launch_count(const dq_ctx* ctx);
+
+/* The rows of one device column whose bit is set in select_bits (device, ceil(nrows / 64) x 8 B), in row order;
+ * nselected must equal the number of set bits. Fixed width: out_values receives nselected elements, out_validity
+ * (may be NULL) ceil(nselected / 64) x 8 B. STRING: two calls — with out_values == NULL, writes out_offsets
+ * (nselected + 1 int32, device), out_validity and *out_bytes; then with out_values (>= *out_bytes + 16 bytes) and the
+ * same out_offsets, copies the bytes and zeroes the 16 bytes after them. */
+int dq_gather_rows(dq_ctx* ctx, const dq_column* column, int64_t nrows, const uint8_t* select_bits, int64_t nselected,
+                   void* out_values, uint8_t* out_validity, int32_t* out_offsets, int64_t* out_bytes);
+
+/* The validator's casts of one cell, host only (no context, no device): 1 = value (written to *out), 0 = NULL,
+ * 2 = ambiguous. */
+int dq_parse_int32(const uint8_t* s, int32_t n, int32_t* out);
+int dq_parse_decimal(const uint8_t* s, int32_t n, int32_t precision, int32_t scale, int64_t* out);
+int dq_parse_timestamp(const uint8_t* program, int32_t program_len, const uint8_t* s, int32_t n, int64_t* out);
+
 /* Multi-GPU grouping: the canonical 64-bit keys (see DQ_FREQ_KEYS_VALUES) of one
  * fixed-width column's non-NULL rows, bucketed by owner rank = (mix64(key) >> 32) % nparts, written
  * contiguously per rank into keys_dev (capacity nrows, device memory) for an RCCL all-to-all; the
