@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "dq_common.h"
+#include "dq_device.h"
 #include "dq_internal.h"
 #include "dq_parse.h"
 
@@ -42,10 +43,6 @@ __device__ __forceinline__ int64_t java_d2l(double d) {
     if (d <= -9223372036854775808.0) return INT64_MIN;
     return (int64_t)d;
 }
-
-// Bytes of one wave's 64 consecutive strings staged in LDS by coalesced dword loads (the parsers then read LDS, not
-// scattered HBM bytes); a longer range is parsed from HBM directly.
-constexpr int kCastStageWords = 512;
 
 // ---- short numeric strings without per-byte branches (r06) ---------------------------------------------------------
 // The numeric-looking string columns a profile casts hold short plain numbers ("-4999", "123.45"). For a string of
@@ -127,7 +124,7 @@ template <bool STRING>
 __global__ void __launch_bounds__(kCastBlock)
 cast_kernel(CastSource c, int64_t nrows, int to_double, void* __restrict__ values_out,
             uint64_t* __restrict__ validity_out, unsigned int* __restrict__ slow_flag, int no_short) {
-    __shared__ uint32_t stage[STRING ? kCastBlock / 64 : 1][STRING ? kCastStageWords : 1];
+    __shared__ uint32_t stage[STRING ? kCastBlock / 64 : 1][STRING ? kStageWords : 1];
     const int64_t stride = (int64_t)gridDim.x * kCastBlock;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int64_t base = (int64_t)blockIdx.x * kCastBlock; base < nrows; base += stride) {
@@ -140,7 +137,7 @@ cast_kernel(CastSource c, int64_t nrows, int to_double, void* __restrict__ value
         // the row's validity and (STRING) its offsets, loaded before the staging: with the wave's range bounds they
         // are one memory round trip, not a third one after the stage's barrier
         const bool rin = r < nrows;
-        const bool rvalid = rin && (c.validity == nullptr || ((c.validity[r >> 6] >> (r & 63)) & 1ull));
+        const bool rvalid = rin && row_valid(c.validity, r);
         int32_t ro = 0, rlen = 0;
         if (STRING && rin) {
             ro = c.offsets[r];
@@ -148,19 +145,9 @@ cast_kernel(CastSource c, int64_t nrows, int to_double, void* __restrict__ value
         }
         if (STRING) {
             const int64_t w0 = base + 64 * wave;
-            if (w0 < nrows) {
+            if (w0 < nrows) {  // wave-uniform
                 const int64_t wl = w0 + 64 < nrows ? w0 + 64 : nrows;
-                const int64_t b0 = c.offsets[w0], b1 = c.offsets[wl];
-                a0 = b0 & ~(int64_t)3;
-                const int64_t nwords = (b1 - a0 + 3) >> 2;  // dwords holding [b0, b1): nothing past the last byte
-                if (nwords <= kCastStageWords) {
-                    const uint32_t* src = reinterpret_cast<const uint32_t*>(c.bytes + a0);
-                    for (int64_t i = lane; i < nwords; i += 64) stage[wave][i] = src[i];
-                    sbase = reinterpret_cast<const uint8_t*>(&stage[wave][0]);
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                sbase = stage_wave_bytes(stage[wave], c.bytes, c.offsets, w0, wl, lane, a0);
             }
         }
         ShortNum sn;
@@ -223,38 +210,7 @@ cast_kernel(CastSource c, int64_t nrows, int to_double, void* __restrict__ value
     }
 }
 
-hipStream_t ctx_stream(dq_ctx* ctx);
-int ctx_device(dq_ctx* ctx);
-int ctx_fail(dq_ctx* ctx, int code, const char* msg);
-int ctx_cus(dq_ctx* ctx);
-
 }  // namespace dq
-
-namespace {
-// Per-call device buffers from the context's scratch cache: a hipFree per cast waited for the whole device, so a cast
-// stalled behind every other context's running kernels (the C5 step's casts sat idle for ~20 ms between columns).
-struct CBuffers {
-    dq_ctx* ctx;
-    std::vector<std::pair<void*, size_t>> ptrs;
-    explicit CBuffers(dq_ctx* c) : ctx(c) {}
-    ~CBuffers() {
-        for (const auto& p : ptrs) dq::scratch_release(ctx, p.first, p.second);
-    }
-    hipError_t alloc(void** p, size_t bytes) {
-        bytes = std::max<size_t>(bytes, 16);
-        *p = dq::scratch_alloc(ctx, bytes);
-        if (!*p) return hipErrorOutOfMemory;
-        ptrs.push_back({*p, bytes});
-        return hipSuccess;
-    }
-};
-}  // namespace
-
-#define CA_HIP(ctx, expr)                                                                         \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return dq::ctx_fail((ctx), DQ_ERR_DEVICE, hipGetErrorString(e_));   \
-    } while (0)
 
 extern "C" {
 
@@ -321,9 +277,9 @@ static int cast_single(dq_ctx* ctx, const dq_column* column, int64_t nrows, int3
     if (((uintptr_t)values_dev & 7) || ((uintptr_t)validity_dev & 7))
         return dq::ctx_fail(ctx, DQ_ERR_ALIGNMENT, "dq_cast_column: output buffers must be 8-B aligned");
     if (nrows == 0) return DQ_OK;
-    CA_HIP(ctx, hipSetDevice(dq::ctx_device(ctx)));
+    DQ_CTX_HIP(ctx, hipSetDevice(dq::ctx_device(ctx)));
     hipStream_t s = dq::ctx_stream(ctx);
-    CBuffers buf(ctx);
+    dq::ScratchBuffers buf(ctx);
     if (column->flags & DQ_COL_OFFSETS64)
         return dq::ctx_fail(ctx, DQ_ERR_UNSUPPORTED, "dq_cast_column: int64 string offsets are for the grouping builds only");
     dq::CastSource c;
@@ -341,20 +297,20 @@ static int cast_single(dq_ctx* ctx, const dq_column* column, int64_t nrows, int3
         void *b = nullptr, *o = nullptr, *m = nullptr;
         if (is_string) {
             const int32_t total = column->offsets[nrows];
-            CA_HIP(ctx, buf.alloc(&b, (size_t)total + 16));
-            CA_HIP(ctx, buf.alloc(&o, sizeof(int32_t) * (size_t)(nrows + 1)));
-            if (total > 0) CA_HIP(ctx, hipMemcpyAsync(b, column->values, (size_t)total, hipMemcpyHostToDevice, s));
-            CA_HIP(ctx, hipMemcpyAsync(o, column->offsets, sizeof(int32_t) * (size_t)(nrows + 1), hipMemcpyHostToDevice, s));
+            DQ_CTX_HIP(ctx, buf.alloc(&b, (size_t)total + 16));
+            DQ_CTX_HIP(ctx, buf.alloc(&o, sizeof(int32_t) * (size_t)(nrows + 1)));
+            if (total > 0) DQ_CTX_HIP(ctx, hipMemcpyAsync(b, column->values, (size_t)total, hipMemcpyHostToDevice, s));
+            DQ_CTX_HIP(ctx, hipMemcpyAsync(o, column->offsets, sizeof(int32_t) * (size_t)(nrows + 1), hipMemcpyHostToDevice, s));
         } else {
             const size_t vb = (size_t)nrows * dq::elem_size(c.elem);
-            CA_HIP(ctx, buf.alloc(&b, vb));
-            CA_HIP(ctx, hipMemcpyAsync(b, column->values, vb, hipMemcpyHostToDevice, s));
+            DQ_CTX_HIP(ctx, buf.alloc(&b, vb));
+            DQ_CTX_HIP(ctx, hipMemcpyAsync(b, column->values, vb, hipMemcpyHostToDevice, s));
         }
         if (column->validity) {
             const size_t bb = (size_t)(nrows + 63) / 64 * 8;
-            CA_HIP(ctx, buf.alloc(&m, bb));
-            CA_HIP(ctx, hipMemsetAsync(m, 0, bb, s));
-            CA_HIP(ctx, hipMemcpyAsync(m, column->validity, (size_t)(nrows + 7) / 8, hipMemcpyHostToDevice, s));
+            DQ_CTX_HIP(ctx, buf.alloc(&m, bb));
+            DQ_CTX_HIP(ctx, hipMemsetAsync(m, 0, bb, s));
+            DQ_CTX_HIP(ctx, hipMemcpyAsync(m, column->validity, (size_t)(nrows + 7) / 8, hipMemcpyHostToDevice, s));
         }
         c.values = b;
         c.bytes = (const uint8_t*)b;
@@ -362,8 +318,8 @@ static int cast_single(dq_ctx* ctx, const dq_column* column, int64_t nrows, int3
         c.validity = (const uint64_t*)m;
     }
     unsigned int* dslow = nullptr;
-    CA_HIP(ctx, buf.alloc((void**)&dslow, sizeof(unsigned int)));
-    CA_HIP(ctx, hipMemsetAsync(dslow, 0, sizeof(unsigned int), s));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&dslow, sizeof(unsigned int)));
+    DQ_CTX_HIP(ctx, hipMemsetAsync(dslow, 0, sizeof(unsigned int), s));
     const int64_t blocks = (nrows + dq::kCastBlock - 1) / dq::kCastBlock;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(blocks, (int64_t)dq::ctx_cus(ctx) * 16));
     const int to_double = to_type == DQ_TYPE_DOUBLE ? 1 : 0;
@@ -374,10 +330,10 @@ static int cast_single(dq_ctx* ctx, const dq_column* column, int64_t nrows, int3
     else
         hipLaunchKernelGGL(dq::cast_kernel<false>, dim3(grid), dim3(dq::kCastBlock), 0, s, c, nrows, to_double,
                            values_dev, (uint64_t*)validity_dev, dslow, no_short);
-    CA_HIP(ctx, hipGetLastError());
+    DQ_CTX_HIP(ctx, hipGetLastError());
     unsigned int slow = 0;
-    CA_HIP(ctx, hipMemcpyAsync(&slow, dslow, sizeof(slow), hipMemcpyDeviceToHost, s));
-    CA_HIP(ctx, hipStreamSynchronize(s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(&slow, dslow, sizeof(slow), hipMemcpyDeviceToHost, s));
+    DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
     if (slow)
         return dq::ctx_fail(ctx, DQ_ERR_UNSUPPORTED,
                             "dq_cast_column: a value needs the arbitrary-precision path of Double.parseDouble "

@@ -23,6 +23,7 @@
 
 #include "dq_common.h"
 #include "dq_internal.h"
+#include "rx_engine.h"
 
 #include <execinfo.h>
 #include <signal.h>
@@ -646,8 +647,9 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
         if (pr.code_len == 4 && pr.code[2] == DQ_P_REGEX) {
             const int c = pr.code[1], k = pr.code[3];
             if (pr.code[0] != DQ_P_COL || !col_ok(c) || k < 0 || k >= pr.n_consts || pr.consts[k].tag != DQ_V_STRING ||
-                pr.consts[k].str_len < 32 || (pr.consts[k].str_offset & 3) ||
-                pr.consts[k].str_offset + pr.consts[k].str_len > pr.strings_len)
+                pr.consts[k].str_offset < 0 || (pr.consts[k].str_offset & 3) ||
+                pr.consts[k].str_offset + pr.consts[k].str_len > pr.strings_len ||
+                !dq::rx::rx_image_ok(pr.strings + pr.consts[k].str_offset, pr.consts[k].str_len))
                 return fail(ctx, DQ_ERR_PREDICATE, "predicate %d: malformed REGEX program", p);
             const int t = columns[c].spark_type;
             if (t < DQ_TYPE_BOOLEAN || t > DQ_TYPE_DECIMAL)
@@ -686,8 +688,10 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
                        op == DQ_P_DAY) {
                 if (op == DQ_P_LIKE && (arg < 0 || arg >= pr.n_consts)) return fail(ctx, DQ_ERR_PREDICATE, "predicate %d: bad LIKE pattern", p);
                 if (op == DQ_P_RLIKE &&
-                    (arg < 0 || arg >= pr.n_consts || pr.consts[arg].tag != DQ_V_STRING || pr.consts[arg].str_len < 32 ||
-                     (pr.consts[arg].str_offset & 3) || pr.consts[arg].str_offset + pr.consts[arg].str_len > pr.strings_len))
+                    (arg < 0 || arg >= pr.n_consts || pr.consts[arg].tag != DQ_V_STRING || pr.consts[arg].str_offset < 0 ||
+                     (pr.consts[arg].str_offset & 3) ||
+                     pr.consts[arg].str_offset + pr.consts[arg].str_len > pr.strings_len ||
+                     !dq::rx::rx_image_ok(pr.strings + pr.consts[arg].str_offset, pr.consts[arg].str_len)))
                     return fail(ctx, DQ_ERR_PREDICATE, "predicate %d: malformed RLIKE program", p);
             } else {
                 --depth;

@@ -244,9 +244,11 @@ inline int rows_per_load_of(int e) {
 }  // namespace dq
 
 #ifdef __cplusplus
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 // The context behind the C-ABI. A single-device context owns one stream, a device arena and pinned staging;
 // a multi-device context (dq_open_devices) owns one single-device sub-context per GPU and, when the devices
@@ -309,6 +311,45 @@ int ctx_fail(dq_ctx* ctx, int code, const char* msg);
 int ctx_cus(dq_ctx* ctx);
 int ctx_num_subs(dq_ctx* ctx);       // devices of a multi-device context (dq_open_devices), 0 for a single-device one
 dq_ctx* ctx_sub(dq_ctx* ctx, int i);  // the single-device context of device i of a multi-device one
+int ctx_side_streams(dq_ctx* ctx, hipStream_t* side, hipEvent_t* fork, hipEvent_t* join);
+void* ctx_scratch(dq_ctx* ctx, size_t bytes);
+void* ctx_pinned_buf(dq_ctx* ctx, size_t bytes);
+
+// Per-call device buffers, released on every exit path: from the context's scratch cache (a hipFree waits for the
+// whole device, stalling the call behind other contexts' kernels), or hipMalloc / hipFree when `ctx` is null (the
+// shards of a multi-device quantile pass). Hidden: an internal type, its inline members are no exports of the library.
+struct __attribute__((visibility("hidden"))) ScratchBuffers {
+    dq_ctx* ctx;
+    std::vector<std::pair<void*, size_t>> ptrs;
+    explicit ScratchBuffers(dq_ctx* c) : ctx(c) {}
+    ScratchBuffers(const ScratchBuffers&) = delete;
+    ScratchBuffers& operator=(const ScratchBuffers&) = delete;
+    ~ScratchBuffers() {
+        for (const auto& p : ptrs) {
+            if (ctx) scratch_release(ctx, p.first, p.second);
+            else (void)hipFree(p.first);
+        }
+    }
+    hipError_t alloc(void** p, size_t bytes) {
+        bytes = std::max<size_t>(bytes, 16);
+        if (ctx) {
+            *p = scratch_alloc(ctx, bytes);
+            if (!*p) return hipErrorOutOfMemory;
+        } else {
+            const hipError_t e = hipMalloc(p, bytes);
+            if (e != hipSuccess) return e;
+        }
+        ptrs.push_back({*p, bytes});
+        return hipSuccess;
+    }
+};
+
+// Return a DQ_ERR_DEVICE failure of `ctx` from the calling function when a HIP call fails.
+#define DQ_CTX_HIP(ctx, expr)                                                                     \
+    do {                                                                                          \
+        hipError_t e_ = (expr);                                                                   \
+        if (e_ != hipSuccess) return dq::ctx_fail((ctx), DQ_ERR_DEVICE, hipGetErrorString(e_));   \
+    } while (0)
 
 // Multi-device orchestration (multi.cpp).
 int multi_scan(dq_ctx* ctx, const dq_column* const* shard_columns, const int64_t* shard_rows, int ncols,

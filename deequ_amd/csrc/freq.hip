@@ -2068,11 +2068,6 @@ row_counts_kernel(LookupTable T, int64_t nrows, long long* __restrict__ out) {
 
 struct dq_ctx;  // defined in dq_api.cpp; only its device/stream are needed here
 extern "C" int dq_set_stream(dq_ctx* ctx, void* stream);
-namespace dq {
-hipStream_t ctx_stream(dq_ctx* ctx);
-int ctx_device(dq_ctx* ctx);
-int ctx_fail(dq_ctx* ctx, int code, const char* msg);
-}
 
 // Key cells of a set of groups as host columns (values / offsets / validity) plus their counts: the groups a
 // device owns in a multi-device table over general keys.
@@ -2174,38 +2169,12 @@ int scan_grid(uint64_t n) {
     return (int)std::max<uint64_t>(1, std::min<uint64_t>(g, 2048));
 }
 
-}  // namespace
-
-#define FQ_HIP(ctx, expr)                                                                         \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return dq::ctx_fail((ctx), DQ_ERR_DEVICE, hipGetErrorString(e_));   \
-    } while (0)
-
-namespace {
-
-struct DevBuf {  // scratch device buffers of one build (the context's scratch cache), released on every path
-    dq_ctx* ctx;
-    std::vector<std::pair<void*, size_t>> ptrs;
-    explicit DevBuf(dq_ctx* c) : ctx(c) {}
-    ~DevBuf() {
-        for (const auto& p : ptrs) dq::scratch_release(ctx, p.first, p.second);
-    }
-    hipError_t alloc(void** p, size_t bytes) {
-        bytes = std::max<size_t>(bytes, 16);
-        *p = dq::scratch_alloc(ctx, bytes);
-        if (!*p) return hipErrorOutOfMemory;
-        ptrs.push_back({*p, bytes});
-        return hipSuccess;
-    }
-};
-
 // extract (+ sizing) -> radix sort on `bits` bits of the keys -> per-bucket LDS aggregation.
 // A bucket whose distinct keys overflow its region (or a fingerprint collision on the general
 // path) restarts the sort/build with more bucket bits (or a new seed).
 // Aggregates the bucketed keys (bucket b = keys[bstart[b], bstart[b] + bcount[b])) into one region per
 // bucket. Returns DQ_OK with *overflow / *collision set from the device counters.
-int build_regions(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, DevBuf& buf, const unsigned long long* sorted,
+int build_regions(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, dq::ScratchBuffers& buf, const unsigned long long* sorted,
                   const unsigned long long* srows, const std::vector<unsigned long long>& bstart,
                   const std::vector<unsigned long long>& bcount, int bits, bool* overflow, bool* collision,
                   const NarrowKey* narrow = nullptr, const unsigned long long* spill = nullptr,
@@ -2237,13 +2206,13 @@ int build_regions(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, DevBuf& buf, con
     t->cap = cap;
     t->bits = bits;
     BuildItem* ditems = nullptr;
-    FQ_HIP(ctx, buf.alloc((void**)&ditems, items.size() * sizeof(BuildItem)));
-    FQ_HIP(ctx, hipMemcpyAsync(ditems, items.data(), items.size() * sizeof(BuildItem), hipMemcpyHostToDevice, s));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&ditems, items.size() * sizeof(BuildItem)));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(ditems, items.data(), items.size() * sizeof(BuildItem), hipMemcpyHostToDevice, s));
     const int nitems = (int)items.size();
     hipLaunchKernelGGL(region_init_kernel, dim3(nitems), dim3(kFreqBlock), 0, s, ditems, nitems, t->slots, t->reps);
     const long long* w = t->ks.weights;
     SummaryPartial* bparts = nullptr;
-    FQ_HIP(ctx, buf.alloc((void**)&bparts, items.size() * sizeof(SummaryPartial)));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&bparts, items.size() * sizeof(SummaryPartial)));
     const double build_n = (double)t->host_ctr.num_rows;  // the count pass's numRows (copied before the build)
     // general keys: every row is verified against its group's representative by verify_items_kernel, one workgroup
     // per work item reading the item's (key, row) pairs from the partition buffers with the item's region L2-resident
@@ -2269,26 +2238,26 @@ int build_regions(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, DevBuf& buf, con
     else
         hipLaunchKernelGGL((build_kernel<false, false>), dim3(nitems), dim3(kBuildBlock), 0, s, ditems, sorted, srows, w,
                            t->slots, t->reps, t->ctr, bparts, build_n, NarrowKey{});
-    FQ_HIP(ctx, hipGetLastError());
+    DQ_CTX_HIP(ctx, hipGetLastError());
     if (nspill) {
         const int grid = (int)std::min<unsigned long long>((nspill + kSpillChunk - 1) / kSpillChunk, 2048);
         hipLaunchKernelGGL(spill_insert_kernel, dim3(grid), dim3(kBuildBlock), 0, s, spill, nspill, t->slots, bits, t->ctr);
-        FQ_HIP(ctx, hipGetLastError());
+        DQ_CTX_HIP(ctx, hipGetLastError());
     }
     if (verify_by_items && nitems > 0) {
         hipLaunchKernelGGL(verify_items_kernel, dim3((unsigned int)nitems), dim3(kVerifyBlock), 0, s,
                            (const BuildItem*)ditems, sorted, srows, t->slots, t->reps, t->ks, t->ctr, tup);
-        FQ_HIP(ctx, hipGetLastError());
+        DQ_CTX_HIP(ctx, hipGetLastError());
     }
     if (general && nrows > 0 && !verify_by_items) {
         const int grid = (int)std::min<int64_t>((nrows + kFreqBlock - 1) / kFreqBlock, 8192);
         hipLaunchKernelGGL(verify_kernel, dim3(grid), dim3(kFreqBlock), 0, s, t->ks, nrows, t->slots, t->reps, bits,
                            t->ctr);
     }
-    FQ_HIP(ctx, hipMemcpyAsync(&t->host_ctr, t->ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(&t->host_ctr, t->ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
     std::vector<SummaryPartial> hparts(items.size());
-    FQ_HIP(ctx, hipMemcpyAsync(hparts.data(), bparts, items.size() * sizeof(SummaryPartial), hipMemcpyDeviceToHost, s));
-    FQ_HIP(ctx, hipStreamSynchronize(s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(hparts.data(), bparts, items.size() * sizeof(SummaryPartial), hipMemcpyDeviceToHost, s));
+    DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
     // the fused summary (exact fixed-point terms: any fold order gives the same bits) unless a split bucket needs
     // the table scan
     t->pre_valid = 0;
@@ -2311,15 +2280,15 @@ int build_regions(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, DevBuf& buf, con
             unsigned int* dsb = nullptr;
             SummaryPartial* dsp = nullptr;
             const size_t nsb = split_buckets.size();
-            FQ_HIP(ctx, buf.alloc((void**)&dsb, nsb * sizeof(unsigned int)));
-            FQ_HIP(ctx, buf.alloc((void**)&dsp, nsb * sizeof(SummaryPartial)));
-            FQ_HIP(ctx, hipMemcpyAsync(dsb, split_buckets.data(), nsb * sizeof(unsigned int), hipMemcpyHostToDevice, s));
+            DQ_CTX_HIP(ctx, buf.alloc((void**)&dsb, nsb * sizeof(unsigned int)));
+            DQ_CTX_HIP(ctx, buf.alloc((void**)&dsp, nsb * sizeof(SummaryPartial)));
+            DQ_CTX_HIP(ctx, hipMemcpyAsync(dsb, split_buckets.data(), nsb * sizeof(unsigned int), hipMemcpyHostToDevice, s));
             hipLaunchKernelGGL(region_summary_kernel, dim3((unsigned int)nsb), dim3(kFreqBlock), 0, s,
                                (const unsigned int*)dsb, (const Slot*)t->slots, build_n, dsp);
-            FQ_HIP(ctx, hipGetLastError());
+            DQ_CTX_HIP(ctx, hipGetLastError());
             std::vector<SummaryPartial> hsp(nsb);
-            FQ_HIP(ctx, hipMemcpyAsync(hsp.data(), dsp, nsb * sizeof(SummaryPartial), hipMemcpyDeviceToHost, s));
-            FQ_HIP(ctx, hipStreamSynchronize(s));
+            DQ_CTX_HIP(ctx, hipMemcpyAsync(hsp.data(), dsp, nsb * sizeof(SummaryPartial), hipMemcpyDeviceToHost, s));
+            DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
             for (const SummaryPartial& p : hsp) summary_merge(acc, p);
         } else if (!split_buckets.empty()) {
             all = false;
@@ -2343,18 +2312,18 @@ int build_regions(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, DevBuf& buf, con
         Counters c = t->host_ctr;
         c.overflow = 0;
         c.mismatch = 0;
-        FQ_HIP(ctx, hipMemcpyAsync(t->ctr, &c, sizeof(Counters), hipMemcpyHostToDevice, s));
-        FQ_HIP(ctx, hipStreamSynchronize(s));  // `c` lives on this stack frame
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(t->ctr, &c, sizeof(Counters), hipMemcpyHostToDevice, s));
+        DQ_CTX_HIP(ctx, hipStreamSynchronize(s));  // `c` lives on this stack frame
     }
     return DQ_OK;
 }
 
 // Small general tables (bits = 0): small_build_kernel + small_check_kernel, the table one region. *overflow sends the
 // caller to the regular path, *collision to a new seed.
-int build_small(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, double est, DevBuf& buf, bool* overflow, bool* collision,
+int build_small(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, double est, dq::ScratchBuffers& buf, bool* overflow, bool* collision,
                 bool count_rows = false) {
     hipStream_t s = dq::ctx_stream(ctx);
-    if (count_rows) FQ_HIP(ctx, hipMemsetAsync(t->ctr, 0, sizeof(Counters), s));
+    if (count_rows) DQ_CTX_HIP(ctx, hipMemsetAsync(t->ctr, 0, sizeof(Counters), s));
     release_slots(t, ctx);
     t->home = ctx;
     t->slots_bytes = kRegion * sizeof(Slot);
@@ -2372,11 +2341,11 @@ int build_small(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, double est, DevBuf
         1, std::min<int64_t>(str1 ? kSmallGrid / 3 * 4 : kSmallGrid, (nrows + kSmallTile - 1) / kSmallTile));
     BuildItem* ditem = nullptr;
     unsigned long long *wk = nullptr, *wr = nullptr;
-    FQ_HIP(ctx, buf.alloc((void**)&ditem, sizeof(BuildItem)));
-    FQ_HIP(ctx, buf.alloc((void**)&wk, (size_t)grid * kRegion * 8));
-    FQ_HIP(ctx, buf.alloc((void**)&wr, (size_t)grid * kRegion * 8));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&ditem, sizeof(BuildItem)));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&wk, (size_t)grid * kRegion * 8));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&wr, (size_t)grid * kRegion * 8));
     const BuildItem it = {0ull, 0ull, 0u, 1u};  // split = 1: region_init clears region 0
-    FQ_HIP(ctx, hipMemcpyAsync(ditem, &it, sizeof(it), hipMemcpyHostToDevice, s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(ditem, &it, sizeof(it), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(region_init_kernel, dim3(1), dim3(kFreqBlock), 0, s, ditem, 1, t->slots, t->reps);
     ctx->freq_paths[DQ_FREQ_PATH_SMALL]++;
     if (str1)
@@ -2390,9 +2359,9 @@ int build_small(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, double est, DevBuf
         hipLaunchKernelGGL((small_build_kernel<kRegion>), dim3(grid), dim3(kBuildBlock), 0, s, t->ks, nrows, t->slots,
                            t->reps, wk, wr, t->ctr, count_rows ? 1 : 0);
     hipLaunchKernelGGL(small_check_kernel, dim3(grid), dim3(kBuildBlock), 0, s, t->ks, t->slots, t->reps, wk, wr, t->ctr);
-    FQ_HIP(ctx, hipGetLastError());
-    FQ_HIP(ctx, hipMemcpyAsync(&t->host_ctr, t->ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
-    FQ_HIP(ctx, hipStreamSynchronize(s));
+    DQ_CTX_HIP(ctx, hipGetLastError());
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(&t->host_ctr, t->ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
+    DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
     t->pre_valid = 0;  // the summary scans the one region
     if (getenv("DQ_DEBUG_FREQ"))
         fprintf(stderr, "[freq small] rows=%lld grid=%d rows_taken=%llu ovf=%llu mis=%llu\n", (long long)nrows, grid,
@@ -2403,8 +2372,8 @@ int build_small(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, double est, DevBuf
         Counters c = t->host_ctr;
         c.overflow = 0;
         c.mismatch = 0;
-        FQ_HIP(ctx, hipMemcpyAsync(t->ctr, &c, sizeof(Counters), hipMemcpyHostToDevice, s));
-        FQ_HIP(ctx, hipStreamSynchronize(s));  // `c` lives on this stack frame
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(t->ctr, &c, sizeof(Counters), hipMemcpyHostToDevice, s));
+        DQ_CTX_HIP(ctx, hipStreamSynchronize(s));  // `c` lives on this stack frame
     }
     return DQ_OK;
 }
@@ -2413,17 +2382,17 @@ int build_small(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, double est, DevBuf
 // per-workgroup digit histograms) -> buckets (pass 2 on the next bits - 8 bits) -> regions.
 constexpr int kMaxPartBits = 20;
 
-int build_partitioned(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, DevBuf& buf, int xgrid, const unsigned int* hist1,
+int build_partitioned(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, dq::ScratchBuffers& buf, int xgrid, const unsigned int* hist1,
                       unsigned long long n, int bits, bool* collision, const unsigned long long* hrow = nullptr,
                       const unsigned long long* tup = nullptr) {
     hipStream_t s = dq::ctx_stream(ctx);
     const bool general = !t->fast || t->ks.weights != nullptr;  // carry row indices (representatives / weights)
     const size_t n_alloc = (size_t)std::max<unsigned long long>(n, 1);
     unsigned long long *off1 = nullptr, *totals = nullptr, *h1 = nullptr, *r1 = nullptr;
-    FQ_HIP(ctx, buf.alloc((void**)&off1, sizeof(unsigned long long) * (size_t)xgrid * kDigitBins));
-    FQ_HIP(ctx, buf.alloc((void**)&totals, sizeof(unsigned long long) * kDigitBins));
-    FQ_HIP(ctx, buf.alloc((void**)&h1, n_alloc * 8));
-    if (general) FQ_HIP(ctx, buf.alloc((void**)&r1, n_alloc * 8));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&off1, sizeof(unsigned long long) * (size_t)xgrid * kDigitBins));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&totals, sizeof(unsigned long long) * kDigitBins));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&h1, n_alloc * 8));
+    if (general) DQ_CTX_HIP(ctx, buf.alloc((void**)&r1, n_alloc * 8));
     hipLaunchKernelGGL(digit_scan_kernel, dim3(kDigitBins), dim3(256), 0, s, hist1, xgrid, kDigitBins, off1, totals);
     if (general)
         hipLaunchKernelGGL((partition1_kernel<true, kPartTile>), dim3(xgrid), dim3(kFreqBlock), 0, s, t->ks, nrows,
@@ -2432,10 +2401,10 @@ int build_partitioned(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, DevBuf& buf,
         hipLaunchKernelGGL((partition1_kernel<false, kPartTile>), dim3(xgrid), dim3(kFreqBlock), 0, s, t->ks, nrows,
                            (const unsigned long long*)off1, (const unsigned long long*)totals, h1, r1,
                            (const unsigned long long*)nullptr);
-    FQ_HIP(ctx, hipGetLastError());
+    DQ_CTX_HIP(ctx, hipGetLastError());
     std::vector<unsigned long long> tot(kDigitBins), pbegin(kDigitBins + 1, 0);
-    FQ_HIP(ctx, hipMemcpyAsync(tot.data(), totals, sizeof(unsigned long long) * kDigitBins, hipMemcpyDeviceToHost, s));
-    FQ_HIP(ctx, hipStreamSynchronize(s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(tot.data(), totals, sizeof(unsigned long long) * kDigitBins, hipMemcpyDeviceToHost, s));
+    DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
     for (int d = 0; d < kDigitBins; ++d) pbegin[d + 1] = pbegin[d] + tot[d];
     unsigned long long *h2 = nullptr, *r2 = nullptr;
     for (int grow = 0; grow < 8 && bits <= kMaxPartBits; ++grow, ++bits) {
@@ -2463,20 +2432,20 @@ int build_partitioned(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, DevBuf& buf,
             unsigned long long *dpbegin = nullptr, *off2 = nullptr, *dbstart = nullptr, *dbcount = nullptr;
             unsigned int* cnt2 = nullptr;
             const uint64_t nb = 1ull << bits;
-            FQ_HIP(ctx, buf.alloc((void**)&ditems, sizeof(Pass2Item) * std::max(nitems, 1)));
-            FQ_HIP(ctx, buf.alloc((void**)&dpitems, sizeof(int) * (kDigitBins + 1)));
-            FQ_HIP(ctx, buf.alloc((void**)&dpbegin, sizeof(unsigned long long) * kDigitBins));
-            FQ_HIP(ctx, buf.alloc((void**)&cnt2, sizeof(unsigned int) * (size_t)std::max(nitems, 1) * BINS));
-            FQ_HIP(ctx, buf.alloc((void**)&off2, sizeof(unsigned long long) * (size_t)std::max(nitems, 1) * BINS));
-            FQ_HIP(ctx, buf.alloc((void**)&dbstart, sizeof(unsigned long long) * nb));
-            FQ_HIP(ctx, buf.alloc((void**)&dbcount, sizeof(unsigned long long) * nb));
+            DQ_CTX_HIP(ctx, buf.alloc((void**)&ditems, sizeof(Pass2Item) * std::max(nitems, 1)));
+            DQ_CTX_HIP(ctx, buf.alloc((void**)&dpitems, sizeof(int) * (kDigitBins + 1)));
+            DQ_CTX_HIP(ctx, buf.alloc((void**)&dpbegin, sizeof(unsigned long long) * kDigitBins));
+            DQ_CTX_HIP(ctx, buf.alloc((void**)&cnt2, sizeof(unsigned int) * (size_t)std::max(nitems, 1) * BINS));
+            DQ_CTX_HIP(ctx, buf.alloc((void**)&off2, sizeof(unsigned long long) * (size_t)std::max(nitems, 1) * BINS));
+            DQ_CTX_HIP(ctx, buf.alloc((void**)&dbstart, sizeof(unsigned long long) * nb));
+            DQ_CTX_HIP(ctx, buf.alloc((void**)&dbcount, sizeof(unsigned long long) * nb));
             if (nitems)
-                FQ_HIP(ctx, hipMemcpyAsync(ditems, items.data(), sizeof(Pass2Item) * nitems, hipMemcpyHostToDevice, s));
-            FQ_HIP(ctx, hipMemcpyAsync(dpitems, pitems.data(), sizeof(int) * (kDigitBins + 1), hipMemcpyHostToDevice, s));
-            FQ_HIP(ctx, hipMemcpyAsync(dpbegin, pbegin.data(), sizeof(unsigned long long) * kDigitBins, hipMemcpyHostToDevice, s));
+                DQ_CTX_HIP(ctx, hipMemcpyAsync(ditems, items.data(), sizeof(Pass2Item) * nitems, hipMemcpyHostToDevice, s));
+            DQ_CTX_HIP(ctx, hipMemcpyAsync(dpitems, pitems.data(), sizeof(int) * (kDigitBins + 1), hipMemcpyHostToDevice, s));
+            DQ_CTX_HIP(ctx, hipMemcpyAsync(dpbegin, pbegin.data(), sizeof(unsigned long long) * kDigitBins, hipMemcpyHostToDevice, s));
             if (!h2) {
-                FQ_HIP(ctx, buf.alloc((void**)&h2, n_alloc * 8));
-                if (general) FQ_HIP(ctx, buf.alloc((void**)&r2, n_alloc * 8));
+                DQ_CTX_HIP(ctx, buf.alloc((void**)&h2, n_alloc * 8));
+                if (general) DQ_CTX_HIP(ctx, buf.alloc((void**)&r2, n_alloc * 8));
             }
             const unsigned int mask = (unsigned int)bins - 1;
             if (big) {
@@ -2500,12 +2469,12 @@ int build_partitioned(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, DevBuf& buf,
                     hipLaunchKernelGGL((scatter2_kernel<kDigitBins, false, kPartTileFast>), dim3(nitems), dim3(kFreqBlock), 0, s, ditems, off2, h1, r1,
                                        8, mask, h2, r2);
             }
-            FQ_HIP(ctx, hipGetLastError());
+            DQ_CTX_HIP(ctx, hipGetLastError());
             bstart.resize(nb);
             bcount.resize(nb);
-            FQ_HIP(ctx, hipMemcpyAsync(bstart.data(), dbstart, sizeof(unsigned long long) * nb, hipMemcpyDeviceToHost, s));
-            FQ_HIP(ctx, hipMemcpyAsync(bcount.data(), dbcount, sizeof(unsigned long long) * nb, hipMemcpyDeviceToHost, s));
-            FQ_HIP(ctx, hipStreamSynchronize(s));
+            DQ_CTX_HIP(ctx, hipMemcpyAsync(bstart.data(), dbstart, sizeof(unsigned long long) * nb, hipMemcpyDeviceToHost, s));
+            DQ_CTX_HIP(ctx, hipMemcpyAsync(bcount.data(), dbcount, sizeof(unsigned long long) * nb, hipMemcpyDeviceToHost, s));
+            DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
             sorted = h2;
             srows = r2;
         }
@@ -2560,7 +2529,7 @@ narrow_sample_kernel(KeyCol c, int64_t nrows, long long* __restrict__ out) {
 }
 
 // The narrow-key window for the fast path's key column (see NarrowKey), or false for 64-bit keys.
-bool choose_narrow(dq_ctx* ctx, const dq_freq_table* t, int64_t nrows, DevBuf& buf, NarrowKey* nk, int* rc) {
+bool choose_narrow(dq_ctx* ctx, const dq_freq_table* t, int64_t nrows, dq::ScratchBuffers& buf, NarrowKey* nk, int* rc) {
     *rc = DQ_OK;
     const KeyCol& c = t->ks.cols[0];
     const ElemType elem = (ElemType)c.elem;
@@ -2599,7 +2568,7 @@ bool choose_narrow(dq_ctx* ctx, const dq_freq_table* t, int64_t nrows, DevBuf& b
     return true;
 }
 
-int build_fast(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, DevBuf& buf, bool* done, bool allow_narrow = true) {
+int build_fast(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, dq::ScratchBuffers& buf, bool* done, bool allow_narrow = true) {
     *done = false;
     hipStream_t s = dq::ctx_stream(ctx);
     const int xgrid = scan_grid((uint64_t)nrows);
@@ -2620,17 +2589,17 @@ int build_fast(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, DevBuf& buf, bool* 
     void* h1 = nullptr;
     unsigned int* regs = nullptr;
     uint8_t* regs_part = nullptr;
-    FQ_HIP(ctx, buf.alloc((void**)&gc1, sizeof(unsigned long long) * kSub * kCursorStride));
-    FQ_HIP(ctx, buf.alloc((void**)&h1, cap1 * kSub * ksz));
-    FQ_HIP(ctx, buf.alloc((void**)&regs, kFastRegs * sizeof(unsigned int)));
-    FQ_HIP(ctx, buf.alloc((void**)&regs_part, (size_t)kFastRegs * xgrid));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&gc1, sizeof(unsigned long long) * kSub * kCursorStride));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&h1, cap1 * kSub * ksz));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&regs, kFastRegs * sizeof(unsigned int)));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&regs_part, (size_t)kFastRegs * xgrid));
     // spill buffer: room for a quarter of the rows past full buckets (heavily repeated keys); more sends the build to
     // the exactly-counted path
     Spill sp{nullptr, (unsigned long long)nrows / 4 + (1ull << 20), &t->ctr->spilled};
-    FQ_HIP(ctx, buf.alloc((void**)&sp.keys, sp.cap * sizeof(unsigned long long)));
-    FQ_HIP(ctx, hipMemsetAsync(gc1, 0, sizeof(unsigned long long) * kSub * kCursorStride, s));
-    FQ_HIP(ctx, hipMemsetAsync(regs, 0, kFastRegs * sizeof(unsigned int), s));
-    FQ_HIP(ctx, hipMemsetAsync(t->ctr, 0, sizeof(Counters), s));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&sp.keys, sp.cap * sizeof(unsigned long long)));
+    DQ_CTX_HIP(ctx, hipMemsetAsync(gc1, 0, sizeof(unsigned long long) * kSub * kCursorStride, s));
+    DQ_CTX_HIP(ctx, hipMemsetAsync(regs, 0, kFastRegs * sizeof(unsigned int), s));
+    DQ_CTX_HIP(ctx, hipMemsetAsync(t->ctr, 0, sizeof(Counters), s));
     const int inul = t->ks.include_nulls ? 1 : 0;
     // (measured: an 8 K-key pass-1 tile runs 8.1 ms against 6.1 ms for 4 K on C4 -- twice the registers)
 #define DQ_P1(W, N, F)                                                                                              \
@@ -2661,14 +2630,14 @@ int build_fast(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, DevBuf& buf, bool* 
 #undef DQ_P1
     hipLaunchKernelGGL(sizing_reduce_kernel, dim3(kFastRegs / 256, std::min(xgrid, 64)), dim3(256), 0, s,
                        (const uint8_t*)regs_part, xgrid, kFastRegs, regs);
-    FQ_HIP(ctx, hipGetLastError());
+    DQ_CTX_HIP(ctx, hipGetLastError());
     std::vector<unsigned int> hregs(kFastRegs);
     std::vector<unsigned long long> pcount(kSub), pstrided((size_t)kSub * kCursorStride);
-    FQ_HIP(ctx, hipMemcpyAsync(hregs.data(), regs, kFastRegs * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
-    FQ_HIP(ctx, hipMemcpyAsync(pstrided.data(), gc1, sizeof(unsigned long long) * kSub * kCursorStride,
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(hregs.data(), regs, kFastRegs * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(pstrided.data(), gc1, sizeof(unsigned long long) * kSub * kCursorStride,
                                hipMemcpyDeviceToHost, s));
-    FQ_HIP(ctx, hipMemcpyAsync(&t->host_ctr, t->ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
-    FQ_HIP(ctx, hipStreamSynchronize(s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(&t->host_ctr, t->ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
+    DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
     if (t->host_ctr.pad[0]) return DQ_OK;  // the spill buffer overflowed: the exact path
     if (t->host_ctr.narrow_miss) {  // an 8-byte key outside the sampled window: again with 64-bit keys
         if (getenv("DQ_DEBUG_FREQ"))
@@ -2720,16 +2689,16 @@ int build_fast(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, DevBuf& buf, bool* 
             const int nitems = (int)items.size();
             FastItem* ditems = nullptr;
             unsigned long long* gc2 = nullptr;
-            FQ_HIP(ctx, buf.alloc((void**)&ditems, sizeof(FastItem) * std::max(nitems, 1)));
-            FQ_HIP(ctx, buf.alloc((void**)&gc2, sizeof(unsigned long long) * nb));
+            DQ_CTX_HIP(ctx, buf.alloc((void**)&ditems, sizeof(FastItem) * std::max(nitems, 1)));
+            DQ_CTX_HIP(ctx, buf.alloc((void**)&gc2, sizeof(unsigned long long) * nb));
             if (cap2 * nb * ksz > h2_bytes) {
                 h2_bytes = cap2 * nb * ksz;
-                FQ_HIP(ctx, buf.alloc((void**)&h2, h2_bytes));
+                DQ_CTX_HIP(ctx, buf.alloc((void**)&h2, h2_bytes));
             }
-            FQ_HIP(ctx, hipMemsetAsync(gc2, 0, sizeof(unsigned long long) * nb, s));
+            DQ_CTX_HIP(ctx, hipMemsetAsync(gc2, 0, sizeof(unsigned long long) * nb, s));
             // a retry with more buckets keeps pass 1's spilled keys and drops the previous pass 2's
-            FQ_HIP(ctx, hipMemcpyAsync(&t->ctr->spilled, &spilled1, sizeof(spilled1), hipMemcpyHostToDevice, s));
-            if (nitems) FQ_HIP(ctx, hipMemcpyAsync(ditems, items.data(), sizeof(FastItem) * nitems, hipMemcpyHostToDevice, s));
+            DQ_CTX_HIP(ctx, hipMemcpyAsync(&t->ctr->spilled, &spilled1, sizeof(spilled1), hipMemcpyHostToDevice, s));
+            if (nitems) DQ_CTX_HIP(ctx, hipMemcpyAsync(ditems, items.data(), sizeof(FastItem) * nitems, hipMemcpyHostToDevice, s));
             const unsigned int mask = (unsigned int)bins - 1;
 #define DQ_P2(B, T, N)                                                                                            \
     hipLaunchKernelGGL((scatter2_fast_kernel<B, T, N>), dim3(nitems), dim3(kFreqBlock), 0, s, ditems, h1, mask, cap2, \
@@ -2740,11 +2709,11 @@ int build_fast(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, DevBuf& buf, bool* 
                 if (narrow) DQ_P2(kDigitBins, kPartTileFast, true); else DQ_P2(kDigitBins, kPartTileFast, false);
             }
 #undef DQ_P2
-            FQ_HIP(ctx, hipGetLastError());
+            DQ_CTX_HIP(ctx, hipGetLastError());
             std::vector<unsigned long long> pb(nb);
-            FQ_HIP(ctx, hipMemcpyAsync(pb.data(), gc2, sizeof(unsigned long long) * nb, hipMemcpyDeviceToHost, s));
-            FQ_HIP(ctx, hipMemcpyAsync(&t->host_ctr, t->ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
-            FQ_HIP(ctx, hipStreamSynchronize(s));
+            DQ_CTX_HIP(ctx, hipMemcpyAsync(pb.data(), gc2, sizeof(unsigned long long) * nb, hipMemcpyDeviceToHost, s));
+            DQ_CTX_HIP(ctx, hipMemcpyAsync(&t->host_ctr, t->ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
+            DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
             if (t->host_ctr.pad[1]) return DQ_OK;  // the spill buffer overflowed: the exact path
             bstart.resize(nb);
             bcount.resize(nb);
@@ -2775,7 +2744,7 @@ int build_fast(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, DevBuf& buf, bool* 
 // general path) restarts with more bucket bits (or a new seed).
 int build_table(dq_ctx* ctx, dq_freq_table* t, int64_t nrows) {
     hipStream_t s = dq::ctx_stream(ctx);
-    DevBuf buf(ctx);
+    dq::ScratchBuffers buf(ctx);
     const bool general = !t->fast || t->ks.weights != nullptr;  // carry row indices (representatives / weights)
     const bool no_partition = getenv("DQ_FREQ_NO_PARTITION") != nullptr;
     if (t->fast && !t->ks.weights && !no_partition && nrows >= kFastMinRows && !getenv("DQ_FREQ_EXACT")) {
@@ -2805,22 +2774,22 @@ int build_table(dq_ctx* ctx, dq_freq_table* t, int64_t nrows) {
         uint8_t* regs_part = nullptr;
         const size_t n_alloc = (size_t)std::max<int64_t>(nrows, 1);
         const int xgrid = scan_grid((uint64_t)std::max<int64_t>(nrows, 1));
-        FQ_HIP(ctx, buf.alloc((void**)&bk, 2 * sizeof(unsigned long long) * xgrid));
-        FQ_HIP(ctx, buf.alloc((void**)&regs, kSizingRegs * sizeof(unsigned int)));
-        FQ_HIP(ctx, buf.alloc((void**)&regs_part, (size_t)kSizingRegs * xgrid));
-        FQ_HIP(ctx, buf.alloc((void**)&hist1, sizeof(unsigned int) * (size_t)xgrid * kDigitBins));
-        FQ_HIP(ctx, hipMemsetAsync(bk, 0, 2 * sizeof(unsigned long long) * xgrid, s));
-        FQ_HIP(ctx, hipMemsetAsync(regs, 0, kSizingRegs * sizeof(unsigned int), s));
-        FQ_HIP(ctx, hipMemsetAsync(t->ctr, 0, sizeof(Counters), s));
+        DQ_CTX_HIP(ctx, buf.alloc((void**)&bk, 2 * sizeof(unsigned long long) * xgrid));
+        DQ_CTX_HIP(ctx, buf.alloc((void**)&regs, kSizingRegs * sizeof(unsigned int)));
+        DQ_CTX_HIP(ctx, buf.alloc((void**)&regs_part, (size_t)kSizingRegs * xgrid));
+        DQ_CTX_HIP(ctx, buf.alloc((void**)&hist1, sizeof(unsigned int) * (size_t)xgrid * kDigitBins));
+        DQ_CTX_HIP(ctx, hipMemsetAsync(bk, 0, 2 * sizeof(unsigned long long) * xgrid, s));
+        DQ_CTX_HIP(ctx, hipMemsetAsync(regs, 0, kSizingRegs * sizeof(unsigned int), s));
+        DQ_CTX_HIP(ctx, hipMemsetAsync(t->ctr, 0, sizeof(Counters), s));
         // general keys of a large table: the count pass writes every row's key and the partition pass reads it back
         // (8 B a row instead of reading and hashing the key columns twice)
         unsigned long long* hrow = nullptr;
-        if (general && many_keys && !getenv("DQ_FREQ_NO_HROW")) FQ_HIP(ctx, buf.alloc((void**)&hrow, n_alloc * 8));
+        if (general && many_keys && !getenv("DQ_FREQ_NO_HROW")) DQ_CTX_HIP(ctx, buf.alloc((void**)&hrow, n_alloc * 8));
         // one string key column: its rows as two-word tuples too, so the verification compares 16-byte tuples
         // instead of both rows' offsets and bytes
         unsigned long long* tup = nullptr;
         if (hrow && t->ks.ncols == 1 && t->ks.cols[0].spark_type == DQ_TYPE_STRING && !getenv("DQ_FREQ_NO_TUPLES"))
-            FQ_HIP(ctx, buf.alloc((void**)&tup, n_alloc * 16));
+            DQ_CTX_HIP(ctx, buf.alloc((void**)&tup, n_alloc * 16));
         ctx->freq_paths[DQ_FREQ_PATH_EXACT]++;
         if (nrows > 0) {
             hipLaunchKernelGGL(extract_count_kernel, dim3(xgrid), dim3(kFreqBlock), 0, s, t->ks, nrows, bk, regs_part,
@@ -2828,13 +2797,13 @@ int build_table(dq_ctx* ctx, dq_freq_table* t, int64_t nrows) {
             hipLaunchKernelGGL(sizing_reduce_kernel, dim3(kSizingRegs / 256, std::min(xgrid, 64)), dim3(256), 0, s,
                                (const uint8_t*)regs_part, xgrid, kSizingRegs, regs);
         }
-        FQ_HIP(ctx, hipGetLastError());
+        DQ_CTX_HIP(ctx, hipGetLastError());
         std::vector<unsigned int> hregs(kSizingRegs);
         std::vector<unsigned long long> hkeep(xgrid), hoff(xgrid);
-        FQ_HIP(ctx, hipMemcpyAsync(hregs.data(), regs, kSizingRegs * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
-        FQ_HIP(ctx, hipMemcpyAsync(hkeep.data(), bk, sizeof(unsigned long long) * xgrid, hipMemcpyDeviceToHost, s));
-        FQ_HIP(ctx, hipMemcpyAsync(&t->host_ctr, t->ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
-        FQ_HIP(ctx, hipStreamSynchronize(s));
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(hregs.data(), regs, kSizingRegs * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(hkeep.data(), bk, sizeof(unsigned long long) * xgrid, hipMemcpyDeviceToHost, s));
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(&t->host_ctr, t->ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
+        DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
         if (tup && t->host_ctr.pad[2]) ctx->freq_paths[DQ_FREQ_PATH_LONG_TUPLES]++;
         unsigned long long n = 0;
         for (int g = 0; g < xgrid; ++g) {
@@ -2867,17 +2836,17 @@ int build_table(dq_ctx* ctx, dq_freq_table* t, int64_t nrows) {
             continue;
         }
         ctx->freq_paths[DQ_FREQ_PATH_SORTED]++;
-        FQ_HIP(ctx, buf.alloc((void**)&hs, n_alloc * 8));
-        if (general) FQ_HIP(ctx, buf.alloc((void**)&rows, n_alloc * 8));
+        DQ_CTX_HIP(ctx, buf.alloc((void**)&hs, n_alloc * 8));
+        if (general) DQ_CTX_HIP(ctx, buf.alloc((void**)&rows, n_alloc * 8));
         if (nrows > 0) {
-            FQ_HIP(ctx, hipMemcpyAsync(bk + xgrid, hoff.data(), sizeof(unsigned long long) * xgrid, hipMemcpyHostToDevice, s));
+            DQ_CTX_HIP(ctx, hipMemcpyAsync(bk + xgrid, hoff.data(), sizeof(unsigned long long) * xgrid, hipMemcpyHostToDevice, s));
             hipLaunchKernelGGL(extract_write_kernel, dim3(xgrid), dim3(kFreqBlock), 0, s, t->ks, nrows,
                                (const unsigned long long*)(bk + xgrid), hs, rows, kPartTile);
-            FQ_HIP(ctx, hipGetLastError());
+            DQ_CTX_HIP(ctx, hipGetLastError());
         }
         unsigned long long *hs2 = nullptr, *rows2 = nullptr;
-        FQ_HIP(ctx, buf.alloc((void**)&hs2, n_alloc * 8));
-        if (general) FQ_HIP(ctx, buf.alloc((void**)&rows2, n_alloc * 8));
+        DQ_CTX_HIP(ctx, buf.alloc((void**)&hs2, n_alloc * 8));
+        if (general) DQ_CTX_HIP(ctx, buf.alloc((void**)&rows2, n_alloc * 8));
         bool overflow = true;
         for (int grow = 0; grow < 8 && overflow; ++grow, ++bits) {
             // ---- sort on the low `bits` bits: each bucket becomes one contiguous run ----------------
@@ -2887,26 +2856,26 @@ int build_table(dq_ctx* ctx, dq_freq_table* t, int64_t nrows) {
                 size_t tmp_bytes = 0;
                 void* tmp = nullptr;
                 if (general) {
-                    FQ_HIP(ctx, rocprim::radix_sort_pairs(nullptr, tmp_bytes, hs, hs2, rows, rows2, (size_t)n, 0u,
+                    DQ_CTX_HIP(ctx, rocprim::radix_sort_pairs(nullptr, tmp_bytes, hs, hs2, rows, rows2, (size_t)n, 0u,
                                                           (unsigned)bits, s));
-                    FQ_HIP(ctx, buf.alloc(&tmp, tmp_bytes));
-                    FQ_HIP(ctx, rocprim::radix_sort_pairs(tmp, tmp_bytes, hs, hs2, rows, rows2, (size_t)n, 0u, (unsigned)bits, s));
+                    DQ_CTX_HIP(ctx, buf.alloc(&tmp, tmp_bytes));
+                    DQ_CTX_HIP(ctx, rocprim::radix_sort_pairs(tmp, tmp_bytes, hs, hs2, rows, rows2, (size_t)n, 0u, (unsigned)bits, s));
                     srows = rows2;
                 } else {
-                    FQ_HIP(ctx, rocprim::radix_sort_keys(nullptr, tmp_bytes, hs, hs2, (size_t)n, 0u, (unsigned)bits, s));
-                    FQ_HIP(ctx, buf.alloc(&tmp, tmp_bytes));
-                    FQ_HIP(ctx, rocprim::radix_sort_keys(tmp, tmp_bytes, hs, hs2, (size_t)n, 0u, (unsigned)bits, s));
+                    DQ_CTX_HIP(ctx, rocprim::radix_sort_keys(nullptr, tmp_bytes, hs, hs2, (size_t)n, 0u, (unsigned)bits, s));
+                    DQ_CTX_HIP(ctx, buf.alloc(&tmp, tmp_bytes));
+                    DQ_CTX_HIP(ctx, rocprim::radix_sort_keys(tmp, tmp_bytes, hs, hs2, (size_t)n, 0u, (unsigned)bits, s));
                 }
                 sorted = hs2;
             }
             const uint64_t nb = 1ull << bits;
             unsigned long long* bounds = nullptr;
-            FQ_HIP(ctx, buf.alloc((void**)&bounds, (nb + 1) * 8));
+            DQ_CTX_HIP(ctx, buf.alloc((void**)&bounds, (nb + 1) * 8));
             hipLaunchKernelGGL(bucket_bounds_kernel, dim3((unsigned)((nb + 1 + 255) / 256)), dim3(256), 0, s, sorted,
                                (uint64_t)n, bits, nb, bounds);
             std::vector<unsigned long long> hb(nb + 1), bstart(nb), bcount(nb);
-            FQ_HIP(ctx, hipMemcpyAsync(hb.data(), bounds, (nb + 1) * 8, hipMemcpyDeviceToHost, s));
-            FQ_HIP(ctx, hipStreamSynchronize(s));
+            DQ_CTX_HIP(ctx, hipMemcpyAsync(hb.data(), bounds, (nb + 1) * 8, hipMemcpyDeviceToHost, s));
+            DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
             for (uint64_t b = 0; b < nb; ++b) {
                 bstart[b] = hb[b];
                 bcount[b] = hb[b + 1] - hb[b];
@@ -2988,14 +2957,14 @@ int multi_local_build(int i, dq_ctx* sub, void* arg) {
     const int64_t got = dq_freq_export_device(sub, t, g, ek, ec);
     if (got < 0) return (int)got;
     unsigned long long* dc = nullptr;
-    FQ_HIP(sub, hipMalloc(&dc, sizeof(unsigned long long) * 128));
-    FQ_HIP(sub, hipMemsetAsync(dc, 0, sizeof(unsigned long long) * 128, s));
+    DQ_CTX_HIP(sub, hipMalloc(&dc, sizeof(unsigned long long) * 128));
+    DQ_CTX_HIP(sub, hipMemsetAsync(dc, 0, sizeof(unsigned long long) * 128, s));
     const int grid = scan_grid((uint64_t)std::max<int64_t>(got, 1));
     if (got) hipLaunchKernelGGL(pair_owner_count_kernel, dim3(grid), dim3(kFreqBlock), 0, s, (const long long*)ek, got,
                                 j->ndev, dc);
     std::vector<unsigned long long> h(64);
-    FQ_HIP(sub, hipMemcpyAsync(h.data(), dc, 64 * 8, hipMemcpyDeviceToHost, s));
-    FQ_HIP(sub, hipStreamSynchronize(s));
+    DQ_CTX_HIP(sub, hipMemcpyAsync(h.data(), dc, 64 * 8, hipMemcpyDeviceToHost, s));
+    DQ_CTX_HIP(sub, hipStreamSynchronize(s));
     std::vector<unsigned long long> cur(64, 0);
     unsigned long long off = 0;
     for (int p = 0; p < j->ndev; ++p) {
@@ -3003,12 +2972,12 @@ int multi_local_build(int i, dq_ctx* sub, void* arg) {
         j->counts[(size_t)i * j->ndev + p] = (int64_t)h[p];
         off += h[p];
     }
-    FQ_HIP(sub, hipMemcpyAsync(dc + 64, cur.data(), 64 * 8, hipMemcpyHostToDevice, s));
+    DQ_CTX_HIP(sub, hipMemcpyAsync(dc + 64, cur.data(), 64 * 8, hipMemcpyHostToDevice, s));
     if (got) hipLaunchKernelGGL(pair_owner_scatter_kernel, dim3(grid), dim3(kFreqBlock), 0, s, (const long long*)ek,
                                 (const long long*)ec, got, j->ndev, dc + 64, (long long*)j->send_keys[i],
                                 (long long*)j->send_cnts[i]);
-    FQ_HIP(sub, hipGetLastError());
-    FQ_HIP(sub, hipStreamSynchronize(s));
+    DQ_CTX_HIP(sub, hipGetLastError());
+    DQ_CTX_HIP(sub, hipStreamSynchronize(s));
     (void)hipFree(ek);
     (void)hipFree(ec);
     (void)hipFree(dc);
@@ -3366,7 +3335,7 @@ int dq_frequencies_ex(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t 
     if (!ctx->subs.empty()) return multi_frequencies(ctx, columns, ncols, nrows, key_columns, nkeys, opt, out);
     *out = nullptr;
     const int dev = dq::ctx_device(ctx);
-    FQ_HIP(ctx, hipSetDevice(dev));
+    DQ_CTX_HIP(ctx, hipSetDevice(dev));
     hipStream_t s = dq::ctx_stream(ctx);
     dq_freq_table* t = new dq_freq_table();
     t->device = dev;
@@ -3402,24 +3371,24 @@ int dq_frequencies_ex(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t 
             size_t vbytes = col.spark_type == DQ_TYPE_STRING ? (size_t)send
                                                               : (size_t)nrows * std::max(1, elem_size(kc.elem));
             void* v = nullptr;
-            FQ_HIP(ctx, hipMalloc(&v, vbytes + 16));
+            DQ_CTX_HIP(ctx, hipMalloc(&v, vbytes + 16));
             staged.push_back(v);
-            if (vbytes) FQ_HIP(ctx, hipMemcpyAsync(v, col.values, vbytes, hipMemcpyHostToDevice, s));
+            if (vbytes) DQ_CTX_HIP(ctx, hipMemcpyAsync(v, col.values, vbytes, hipMemcpyHostToDevice, s));
             kc.values = v;
             if (col.validity) {
                 void* vd = nullptr;
                 const size_t nb = (size_t)(nrows + 7) / 8;
-                FQ_HIP(ctx, hipMalloc(&vd, nb + 8));
+                DQ_CTX_HIP(ctx, hipMalloc(&vd, nb + 8));
                 staged.push_back(vd);
-                if (nb) FQ_HIP(ctx, hipMemcpyAsync(vd, col.validity, nb, hipMemcpyHostToDevice, s));
+                if (nb) DQ_CTX_HIP(ctx, hipMemcpyAsync(vd, col.validity, nb, hipMemcpyHostToDevice, s));
                 kc.validity = (const uint8_t*)vd;
             }
             if (col.spark_type == DQ_TYPE_STRING) {
                 const size_t ow = off64 ? 8 : 4;
                 void* od = nullptr;
-                FQ_HIP(ctx, hipMalloc(&od, ((size_t)nrows + 1) * ow));
+                DQ_CTX_HIP(ctx, hipMalloc(&od, ((size_t)nrows + 1) * ow));
                 staged.push_back(od);
-                FQ_HIP(ctx, hipMemcpyAsync(od, col.offsets, ((size_t)nrows + 1) * ow, hipMemcpyHostToDevice, s));
+                DQ_CTX_HIP(ctx, hipMemcpyAsync(od, col.offsets, ((size_t)nrows + 1) * ow, hipMemcpyHostToDevice, s));
                 kc.offsets = off64 ? nullptr : (const int32_t*)od;
                 kc.offsets64 = off64 ? (const int64_t*)od : nullptr;
             }
@@ -3447,9 +3416,9 @@ static int finish_frequencies(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, cons
             t->ks.weights = reinterpret_cast<const long long*>(opt->weights);
         } else {
             void* w = nullptr;
-            FQ_HIP(ctx, hipMalloc(&w, (size_t)nrows * 8));
+            DQ_CTX_HIP(ctx, hipMalloc(&w, (size_t)nrows * 8));
             staged.push_back(w);
-            FQ_HIP(ctx, hipMemcpyAsync(w, opt->weights, (size_t)nrows * 8, hipMemcpyHostToDevice, s));
+            DQ_CTX_HIP(ctx, hipMemcpyAsync(w, opt->weights, (size_t)nrows * 8, hipMemcpyHostToDevice, s));
             t->ks.weights = reinterpret_cast<const long long*>(w);
         }
     }
@@ -3501,7 +3470,7 @@ int dq_frequencies_parts(dq_ctx* ctx, const dq_column* parts, int nparts, int nc
                             "dq_frequencies_parts: two parts on a one-device context, unweighted (else concatenate)");
     *out = nullptr;
     const int64_t n0 = parts[0].length, n1 = parts[ncols].length;
-    FQ_HIP(ctx, hipSetDevice(dq::ctx_device(ctx)));
+    DQ_CTX_HIP(ctx, hipSetDevice(dq::ctx_device(ctx)));
     dq_freq_table* t = new dq_freq_table();
     t->device = dq::ctx_device(ctx);
     t->src_rows = n0 + n1;
@@ -3570,7 +3539,7 @@ int dq_freq_summarize(dq_ctx* ctx, const dq_freq_table* t, int64_t entropy_rows,
         *out = acc;
         return DQ_OK;
     }
-    FQ_HIP(ctx, hipSetDevice(t->device));
+    DQ_CTX_HIP(ctx, hipSetDevice(t->device));
     hipStream_t s = dq::ctx_stream(ctx);
     const int64_t table_rows = t->num_rows_override >= 0 ? t->num_rows_override : (int64_t)t->host_ctr.num_rows;
     const int64_t n = entropy_rows > 0 ? entropy_rows : table_rows;
@@ -3589,10 +3558,10 @@ int dq_freq_summarize(dq_ctx* ctx, const dq_freq_table* t, int64_t entropy_rows,
         SummaryPartial* parts = (SummaryPartial*)t->scratch;
         const int grid = summary_grid();
         hipLaunchKernelGGL(summary_kernel, dim3(grid), dim3(kFreqBlock), 0, s, t->slots, t->cap, (double)n, parts);
-        FQ_HIP(ctx, hipGetLastError());
+        DQ_CTX_HIP(ctx, hipGetLastError());
         std::vector<SummaryPartial> hp(grid);
-        FQ_HIP(ctx, hipMemcpyAsync(hp.data(), parts, sizeof(SummaryPartial) * grid, hipMemcpyDeviceToHost, s));
-        FQ_HIP(ctx, hipStreamSynchronize(s));
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(hp.data(), parts, sizeof(SummaryPartial) * grid, hipMemcpyDeviceToHost, s));
+        DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
         for (const SummaryPartial& p : hp) summary_merge(acc, p);
     }
     // side groups: the fast path's EMPTY-colliding value and (Histogram) the NULL group; their terms come from the
@@ -3607,10 +3576,10 @@ int dq_freq_summarize(dq_ctx* ctx, const dq_freq_table* t, int64_t entropy_rows,
     if (n > 0 && (side[0] || side[1])) {
         SummaryPartial* d = (SummaryPartial*)t->scratch;
         hipLaunchKernelGGL(side_terms_kernel, dim3(1), dim3(64), 0, s, side[0], side[1], (double)n, d);
-        FQ_HIP(ctx, hipGetLastError());
+        DQ_CTX_HIP(ctx, hipGetLastError());
         SummaryPartial hs;
-        FQ_HIP(ctx, hipMemcpyAsync(&hs, d, sizeof(hs), hipMemcpyDeviceToHost, s));
-        FQ_HIP(ctx, hipStreamSynchronize(s));
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(&hs, d, sizeof(hs), hipMemcpyDeviceToHost, s));
+        DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
         acc.ent += hs.ent;
         acc.nonfinite += hs.nonfinite;
     }
@@ -3651,7 +3620,7 @@ static int64_t compact(dq_ctx* ctx, const dq_freq_table* t, int mode, unsigned l
     if (n == 0) return 0;
     unsigned long long* dk = nullptr;
     unsigned long long* dc = nullptr;
-    DevBuf buf(ctx);  // the context's scratch cache: no device-wide wait of a hipFree per export
+    dq::ScratchBuffers buf(ctx);  // the context's scratch cache: no device-wide wait of a hipFree per export
     if (buf.alloc((void**)&dk, n * 8) != hipSuccess || buf.alloc((void**)&dc, n * 8) != hipSuccess) return -1;
     if (hipMemcpyAsync(offsets, off.data(), kScanBlocks * 8, hipMemcpyHostToDevice, s) != hipSuccess) return -1;
     hipLaunchKernelGGL(compact_kernel, dim3(kScanBlocks), dim3(kFreqBlock), 0, s, t->slots, t->reps, t->cap, mode, thr,
@@ -3778,15 +3747,15 @@ int64_t dq_freq_export_device(dq_ctx* ctx, const dq_freq_table* t, int64_t capac
         return dq::ctx_fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_freq_export_device: invalid arguments");
     if (!t->fast || !t->parts.empty())
         return dq::ctx_fail(ctx, DQ_ERR_UNSUPPORTED, "dq_freq_export_device: needs a single-device table of values");
-    FQ_HIP(ctx, hipSetDevice(t->device));
+    DQ_CTX_HIP(ctx, hipSetDevice(t->device));
     hipStream_t s = dq::ctx_stream(ctx);
     unsigned long long* per_block = (unsigned long long*)((char*)t->scratch + kScanBlocks * sizeof(SummaryPartial));
     unsigned long long* offsets = per_block + kScanBlocks;
     hipLaunchKernelGGL(count_selected_kernel, dim3(kScanBlocks), dim3(kFreqBlock), 0, s, t->slots, t->cap, 2, 0ull,
                        per_block);
     std::vector<unsigned long long> pb(kScanBlocks), off(kScanBlocks);
-    FQ_HIP(ctx, hipMemcpyAsync(pb.data(), per_block, kScanBlocks * 8, hipMemcpyDeviceToHost, s));
-    FQ_HIP(ctx, hipStreamSynchronize(s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(pb.data(), per_block, kScanBlocks * 8, hipMemcpyDeviceToHost, s));
+    DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
     unsigned long long total = 0;
     for (int b = 0; b < kScanBlocks; ++b) {
         off[b] = total;
@@ -3794,20 +3763,20 @@ int64_t dq_freq_export_device(dq_ctx* ctx, const dq_freq_table* t, int64_t capac
     }
     const uint64_t n = std::min<uint64_t>(total, (uint64_t)capacity);
     if (n) {
-        FQ_HIP(ctx, hipMemcpyAsync(offsets, off.data(), kScanBlocks * 8, hipMemcpyHostToDevice, s));
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(offsets, off.data(), kScanBlocks * 8, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(compact_kernel, dim3(kScanBlocks), dim3(kFreqBlock), 0, s, t->slots, (const unsigned long long*)nullptr,
                            t->cap, 2, 0ull, offsets, (unsigned long long)n, (unsigned long long*)keys_dev,
                            (unsigned long long*)counts_dev, 1);
-        FQ_HIP(ctx, hipGetLastError());
+        DQ_CTX_HIP(ctx, hipGetLastError());
     }
     int64_t written = (int64_t)n;
     if (t->host_ctr.sentinel && written < capacity) {
         const int64_t kv[2] = {(int64_t)unmix64(kEmpty), (int64_t)t->host_ctr.sentinel};
-        FQ_HIP(ctx, hipMemcpyAsync(keys_dev + written, &kv[0], 8, hipMemcpyHostToDevice, s));
-        FQ_HIP(ctx, hipMemcpyAsync(counts_dev + written, &kv[1], 8, hipMemcpyHostToDevice, s));
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(keys_dev + written, &kv[0], 8, hipMemcpyHostToDevice, s));
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(counts_dev + written, &kv[1], 8, hipMemcpyHostToDevice, s));
         ++written;
     }
-    FQ_HIP(ctx, hipStreamSynchronize(s));  // kv lives on this stack frame
+    DQ_CTX_HIP(ctx, hipStreamSynchronize(s));  // kv lives on this stack frame
     return written;
 }
 
@@ -3843,17 +3812,17 @@ int dq_freq_merge(dq_ctx* ctx, const dq_freq_table* a, const dq_freq_table* b, d
                             "dq_freq_merge: both tables must be single-device tables of one fixed-width key column");
     if (elem_of(a->key_type) != elem_of(b->key_type) || (a->key_type == DQ_TYPE_DOUBLE) != (b->key_type == DQ_TYPE_DOUBLE))
         return dq::ctx_fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_freq_merge: key types differ");
-    FQ_HIP(ctx, hipSetDevice(a->device));
+    DQ_CTX_HIP(ctx, hipSetDevice(a->device));
     dq_freq_summary sa, sb;
     int rc = dq_freq_summarize(ctx, a, 0, &sa);
     if (rc) return rc;
     rc = dq_freq_summarize(ctx, b, 0, &sb);
     if (rc) return rc;
     const int64_t ca = sa.num_groups - (sa.null_count ? 1 : 0), cb = sb.num_groups - (sb.null_count ? 1 : 0);
-    DevBuf buf(ctx);
+    dq::ScratchBuffers buf(ctx);
     int64_t *k = nullptr, *c = nullptr;
-    FQ_HIP(ctx, buf.alloc((void**)&k, (size_t)std::max<int64_t>(ca + cb, 1) * 8));
-    FQ_HIP(ctx, buf.alloc((void**)&c, (size_t)std::max<int64_t>(ca + cb, 1) * 8));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&k, (size_t)std::max<int64_t>(ca + cb, 1) * 8));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&c, (size_t)std::max<int64_t>(ca + cb, 1) * 8));
     const int64_t na = dq_freq_export_device(ctx, a, ca, k, c);
     if (na < 0) return (int)na;
     const int64_t nb = dq_freq_export_device(ctx, b, cb, k + na, c + na);
@@ -3862,7 +3831,7 @@ int dq_freq_merge(dq_ctx* ctx, const dq_freq_table* a, const dq_freq_table* b, d
                             sa.null_count + sb.null_count, out);
     if (rc == DQ_OK) {
         // the pair arrays are this call's scratch: the merged table only keeps its slots
-        FQ_HIP(ctx, hipStreamSynchronize(dq::ctx_stream(ctx)));
+        DQ_CTX_HIP(ctx, hipStreamSynchronize(dq::ctx_stream(ctx)));
         (*out)->ks.weights = nullptr;
         (*out)->ks.cols[0].values = nullptr;
     }
@@ -3959,7 +3928,7 @@ int dq_freq_mutual_information(dq_ctx* ctx, const dq_freq_table* joint, const dq
 namespace {
 int mi_tables(dq_ctx* ctx, const dq_freq_table* joint, const dq_freq_table* x, const dq_freq_table* y, double* mi,
               int32_t* present) {
-    FQ_HIP(ctx, hipSetDevice(joint->device));
+    DQ_CTX_HIP(ctx, hipSetDevice(joint->device));
     hipStream_t s = dq::ctx_stream(ctx);
     LookupTable X, Y;
     X.slots = x->slots;
@@ -3975,10 +3944,10 @@ int mi_tables(dq_ctx* ctx, const dq_freq_table* joint, const dq_freq_table* x, c
     const int grid = summary_grid();
     hipLaunchKernelGGL(mi_kernel, dim3(grid), dim3(kFreqBlock), 0, s, joint->slots, joint->reps, joint->cap,
                        joint->ks, X, Y, (double)n, parts);
-    FQ_HIP(ctx, hipGetLastError());
+    DQ_CTX_HIP(ctx, hipGetLastError());
     std::vector<SummaryPartial> hp(grid);
-    FQ_HIP(ctx, hipMemcpyAsync(hp.data(), parts, sizeof(SummaryPartial) * grid, hipMemcpyDeviceToHost, s));
-    FQ_HIP(ctx, hipStreamSynchronize(s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(hp.data(), parts, sizeof(SummaryPartial) * grid, hipMemcpyDeviceToHost, s));
+    DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
     SummaryPartial acc = {0, 0, 0, 0, 0, 0};
     for (const SummaryPartial& p : hp) summary_merge(acc, p);
     *mi = acc.nonfinite ? NAN : fx_to_double(acc.ent);
@@ -3995,21 +3964,21 @@ int dq_freq_row_counts(dq_ctx* ctx, const dq_freq_table* t, int64_t* counts, int
     if (nrows != t->src_rows)
         return dq::ctx_fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_freq_row_counts: nrows differs from the table's source rows");
     if (nrows == 0) return DQ_OK;
-    FQ_HIP(ctx, hipSetDevice(t->device));
+    DQ_CTX_HIP(ctx, hipSetDevice(t->device));
     hipStream_t s = dq::ctx_stream(ctx);
     LookupTable T;
     T.slots = t->slots;
     T.ks = t->ks;
     T.sentinel = t->host_ctr.sentinel;
     T.bits = t->bits;
-    DevBuf buf(ctx);
+    dq::ScratchBuffers buf(ctx);
     long long* d = reinterpret_cast<long long*>(counts);
     const bool dev_out = (flags & DQ_FREQ_PAIRS_DEVICE) != 0;
-    if (!dev_out) FQ_HIP(ctx, buf.alloc((void**)&d, (size_t)nrows * 8));
+    if (!dev_out) DQ_CTX_HIP(ctx, buf.alloc((void**)&d, (size_t)nrows * 8));
     hipLaunchKernelGGL(row_counts_kernel, dim3(scan_grid((uint64_t)nrows)), dim3(kFreqBlock), 0, s, T, nrows, d);
-    FQ_HIP(ctx, hipGetLastError());
-    if (!dev_out) FQ_HIP(ctx, hipMemcpyAsync(counts, d, (size_t)nrows * 8, hipMemcpyDeviceToHost, s));
-    FQ_HIP(ctx, hipStreamSynchronize(s));
+    DQ_CTX_HIP(ctx, hipGetLastError());
+    if (!dev_out) DQ_CTX_HIP(ctx, hipMemcpyAsync(counts, d, (size_t)nrows * 8, hipMemcpyDeviceToHost, s));
+    DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
     return DQ_OK;
 }
 
@@ -4094,7 +4063,7 @@ extern "C" int dq_partition_keys(dq_ctx* ctx, const dq_column* column, int64_t n
         column->length != nrows || elem_of(column->spark_type) == ET_NONE || !(column->flags & DQ_COL_DEVICE) ||
         (nrows > 0 && !keys_dev))
         return dq::ctx_fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_partition_keys: invalid arguments (device fixed-width column)");
-    FQ_HIP(ctx, hipSetDevice(dq::ctx_device(ctx)));
+    DQ_CTX_HIP(ctx, hipSetDevice(dq::ctx_device(ctx)));
     hipStream_t s = dq::ctx_stream(ctx);
     KeyCol c;
     c.values = column->values;
@@ -4104,13 +4073,13 @@ extern "C" int dq_partition_keys(dq_ctx* ctx, const dq_column* column, int64_t n
     c.spark_type = column->spark_type;
     c.elem = elem_of(column->spark_type);
     unsigned long long* dev = nullptr;
-    FQ_HIP(ctx, hipMalloc(&dev, sizeof(unsigned long long) * 2 * (kMaxParts + 1)));
-    FQ_HIP(ctx, hipMemsetAsync(dev, 0, sizeof(unsigned long long) * 2 * (kMaxParts + 1), s));
+    DQ_CTX_HIP(ctx, hipMalloc(&dev, sizeof(unsigned long long) * 2 * (kMaxParts + 1)));
+    DQ_CTX_HIP(ctx, hipMemsetAsync(dev, 0, sizeof(unsigned long long) * 2 * (kMaxParts + 1), s));
     const int grid = scan_grid((uint64_t)std::max<int64_t>(nrows, 1));
     if (nrows > 0) hipLaunchKernelGGL(part_count_kernel, dim3(grid), dim3(kFreqBlock), 0, s, c, nrows, nparts, dev);
     unsigned long long h[kMaxParts + 1];
-    FQ_HIP(ctx, hipMemcpyAsync(h, dev, sizeof(h), hipMemcpyDeviceToHost, s));
-    FQ_HIP(ctx, hipStreamSynchronize(s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(h, dev, sizeof(h), hipMemcpyDeviceToHost, s));
+    DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
     unsigned long long cur[kMaxParts + 1] = {0};
     unsigned long long off = 0;
     for (int p = 0; p < nparts; ++p) {
@@ -4120,12 +4089,12 @@ extern "C" int dq_partition_keys(dq_ctx* ctx, const dq_column* column, int64_t n
     }
     if (null_rows) *null_rows = (int64_t)h[kMaxParts];
     unsigned long long* cursors = dev + kMaxParts + 1;
-    FQ_HIP(ctx, hipMemcpyAsync(cursors, cur, sizeof(unsigned long long) * kMaxParts, hipMemcpyHostToDevice, s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(cursors, cur, sizeof(unsigned long long) * kMaxParts, hipMemcpyHostToDevice, s));
     if (nrows > 0)
         hipLaunchKernelGGL(part_scatter_kernel, dim3(grid), dim3(kFreqBlock), 0, s, c, nrows, nparts, cursors,
                            (unsigned long long*)keys_dev);
-    FQ_HIP(ctx, hipGetLastError());
-    FQ_HIP(ctx, hipStreamSynchronize(s));
+    DQ_CTX_HIP(ctx, hipGetLastError());
+    DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
     (void)hipFree(dev);
     return DQ_OK;
 }

@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "dq_common.h"
+#include "dq_device.h"
 #include "dq_internal.h"
 
 namespace dq {
@@ -70,10 +71,6 @@ __device__ __forceinline__ double kll_load(const KllColumn& c, int64_t r) {
         case ET_I16: return (double)static_cast<const int16_t*>(c.values)[r];
         default: return (double)static_cast<const int8_t*>(c.values)[r];
     }
-}
-
-__device__ __forceinline__ bool kll_valid(const KllColumn& c, int64_t r) {
-    return c.validity == nullptr || ((c.validity[r >> 6] >> (r & 63)) & 1ull);
 }
 
 // One column's NULL compaction: its tile counts, tile offsets and total (blockIdx.y of the count / scan launches).
@@ -117,7 +114,7 @@ kll_write_kernel(KllColumn c, int64_t nrows, const unsigned long long* __restric
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int64_t rb = r0; rb < r0 + kKllStageRows && rb < nrows; rb += kKllStageBlock) {
         const int64_t r = rb + threadIdx.x;
-        const bool v = r < nrows && kll_valid(c, r);
+        const bool v = r < nrows && row_valid(c.validity, r);
         const unsigned long long ball = __ballot(v);
         const unsigned int before = (unsigned int)__popcll(ball & ((1ull << lane) - 1ull));
         if (lane == 0) wsum[wave] = (unsigned int)__popcll(ball);
@@ -150,7 +147,7 @@ kll_write_jobs_kernel(const KllCountJob* __restrict__ jobs, int64_t nrows) {
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
         const int64_t r = r0 + (int64_t)q * kKllStageBlock + t;
-        const bool v = r < nrows && kll_valid(c, r);
+        const bool v = r < nrows && row_valid(c.validity, r);
         x[q] = v ? kll_load(c, r) : 0.0;
         bal[q] = __ballot(v);
     }
@@ -624,7 +621,7 @@ __device__ __forceinline__ void kll_stage_rows(const KllColumn& c, int64_t r0, i
             bal[q] = 0;
             if (q < nq) {
                 const int64_t r = c0 + (int64_t)q * T + t;
-                const bool v = r < r1 && kll_valid(c, r);
+                const bool v = r < r1 && row_valid(c.validity, r);
                 const double x = v ? kll_load(c, r) : 0.0;
                 key[q] = RAWBITS ? (uint64_t)__double_as_longlong(x) : kll_key(x);
                 bal[q] = __ballot(v);
@@ -1265,36 +1262,11 @@ int launch_kll_compact(int cls, const double* src, const uint64_t* segs, int nse
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-hipStream_t ctx_stream(dq_ctx* ctx);
-int ctx_device(dq_ctx* ctx);
-int ctx_fail(dq_ctx* ctx, int code, const char* msg);
-int ctx_num_subs(dq_ctx* ctx);
-int ctx_side_streams(dq_ctx* ctx, hipStream_t* side, hipEvent_t* fork, hipEvent_t* join);
-dq_ctx* ctx_sub(dq_ctx* ctx, int i);
-void* ctx_scratch(dq_ctx* ctx, size_t bytes);
-void* ctx_pinned_buf(dq_ctx* ctx, size_t bytes);
-
 }  // namespace dq
 
 namespace {
 
 using namespace dq;
-
-struct KBuffers {  // per-call device buffers from the context's scratch cache (no hipMalloc / hipFree per sketch)
-    dq_ctx* ctx;
-    std::vector<std::pair<void*, size_t>> ptrs;
-    explicit KBuffers(dq_ctx* c) : ctx(c) {}
-    ~KBuffers() {
-        for (const auto& p : ptrs) dq::scratch_release(ctx, p.first, p.second);
-    }
-    hipError_t alloc(void** p, size_t bytes) {
-        bytes = std::max<size_t>(bytes, 16);
-        *p = dq::scratch_alloc(ctx, bytes);
-        if (!*p) return hipErrorOutOfMemory;
-        ptrs.push_back({*p, bytes});
-        return hipSuccess;
-    }
-};
 
 uint64_t host_key(double d) {
     uint64_t u;
@@ -1425,12 +1397,6 @@ void put_f64(std::vector<uint8_t>& o, double d) {
 }
 
 }  // namespace
-
-#define KL_HIP(ctx, expr)                                                                         \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return dq::ctx_fail((ctx), DQ_ERR_DEVICE, hipGetErrorString(e_));   \
-    } while (0)
 
 namespace {
 
@@ -1805,14 +1771,14 @@ static int kll_sketch_batch(dq_ctx* ctx, const dq_column* columns, int ncols, in
             return dq::ctx_fail(ctx, DQ_ERR_UNSUPPORTED, "dq_kll_sketch: Cannot handle column type");
     }
     const int dev = dq::ctx_device(ctx);
-    KL_HIP(ctx, hipSetDevice(dev));
+    DQ_CTX_HIP(ctx, hipSetDevice(dev));
     hipStream_t s = dq::ctx_stream(ctx);
-    KBuffers buf(ctx);
+    dq::ScratchBuffers buf(ctx);
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<KColumnRun> run(ncols);
     const int64_t ntiles = (nrows + kKllStageRows - 1) / kKllStageRows;
     unsigned long long* dtotals = nullptr;
-    KL_HIP(ctx, buf.alloc((void**)&dtotals, sizeof(unsigned long long) * std::max(ncols, 1)));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&dtotals, sizeof(unsigned long long) * std::max(ncols, 1)));
     int ncount = 0;
     std::vector<KllCountJob> jobs;  // every NULL-compacted column's counts: one count and one scan launch for all
     std::vector<int> job_col;
@@ -1827,13 +1793,13 @@ static int kll_sketch_batch(dq_ctx* ctx, const dq_column* columns, int ncols, in
             r.kc.validity = (const uint64_t*)column->validity;
         } else {
             void *v = nullptr, *m = nullptr;
-            KL_HIP(ctx, buf.alloc(&v, vbytes));
-            if (nrows) KL_HIP(ctx, hipMemcpyAsync(v, column->values, vbytes, hipMemcpyHostToDevice, s));
+            DQ_CTX_HIP(ctx, buf.alloc(&v, vbytes));
+            if (nrows) DQ_CTX_HIP(ctx, hipMemcpyAsync(v, column->values, vbytes, hipMemcpyHostToDevice, s));
             if (column->validity) {
-                KL_HIP(ctx, buf.alloc(&m, bbytes));
-                KL_HIP(ctx, hipMemsetAsync(m, 0, bbytes, s));
+                DQ_CTX_HIP(ctx, buf.alloc(&m, bbytes));
+                DQ_CTX_HIP(ctx, hipMemsetAsync(m, 0, bbytes, s));
                 if (nrows)
-                    KL_HIP(ctx, hipMemcpyAsync(m, column->validity, (size_t)(nrows + 7) / 8, hipMemcpyHostToDevice, s));
+                    DQ_CTX_HIP(ctx, hipMemcpyAsync(m, column->validity, (size_t)(nrows + 7) / 8, hipMemcpyHostToDevice, s));
             }
             r.kc.values = v;
             r.kc.validity = (const uint64_t*)m;
@@ -1845,8 +1811,8 @@ static int kll_sketch_batch(dq_ctx* ctx, const dq_column* columns, int ncols, in
             r.n = nrows;
         } else if (nrows > 0) {
             unsigned int* dcounts = nullptr;
-            KL_HIP(ctx, buf.alloc((void**)&dcounts, sizeof(unsigned int) * ntiles));
-            KL_HIP(ctx, buf.alloc((void**)&r.doffs, sizeof(unsigned long long) * ntiles));
+            DQ_CTX_HIP(ctx, buf.alloc((void**)&dcounts, sizeof(unsigned int) * ntiles));
+            DQ_CTX_HIP(ctx, buf.alloc((void**)&r.doffs, sizeof(unsigned long long) * ntiles));
             jobs.push_back(KllCountJob{r.kc, dcounts, r.doffs, dtotals + i, nullptr});
             job_col.push_back(i);
             ++ncount;
@@ -1854,21 +1820,21 @@ static int kll_sketch_batch(dq_ctx* ctx, const dq_column* columns, int ncols, in
     }
     if (ncount) {
         KllCountJob* djobs = nullptr;
-        KL_HIP(ctx, buf.alloc((void**)&djobs, sizeof(KllCountJob) * jobs.size()));
-        KL_HIP(ctx, hipMemcpyAsync(djobs, jobs.data(), sizeof(KllCountJob) * jobs.size(), hipMemcpyHostToDevice, s));
+        DQ_CTX_HIP(ctx, buf.alloc((void**)&djobs, sizeof(KllCountJob) * jobs.size()));
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(djobs, jobs.data(), sizeof(KllCountJob) * jobs.size(), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(kll_count_kernel,
                            dim3((unsigned)((ntiles + kKllCountTilesPerBlock - 1) / kKllCountTilesPerBlock),
                                 (unsigned)jobs.size()),
                            dim3(kKllStageBlock), 0, s, (const KllCountJob*)djobs, nrows, (int64_t)ntiles);
         hipLaunchKernelGGL(kll_scan_kernel, dim3(1, (unsigned)jobs.size()), dim3(1024), 0, s, (const KllCountJob*)djobs,
                            ntiles);
-        KL_HIP(ctx, hipGetLastError());
+        DQ_CTX_HIP(ctx, hipGetLastError());
     }
     if (ncount) {  // one round trip for every column's non-NULL count
         unsigned long long* htotals = static_cast<unsigned long long*>(dq::ctx_pinned_buf(ctx, 8 * (size_t)ncols));
         if (!htotals) return DQ_ERR_OUT_OF_MEMORY;
-        KL_HIP(ctx, hipMemcpyAsync(htotals, dtotals, 8 * (size_t)ncols, hipMemcpyDeviceToHost, s));
-        KL_HIP(ctx, hipStreamSynchronize(s));
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(htotals, dtotals, 8 * (size_t)ncols, hipMemcpyDeviceToHost, s));
+        DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
         for (int i = 0; i < ncols; ++i)
             if (!run[i].zero_copy) run[i].n = nrows > 0 ? (int64_t)htotals[i] : 0;
     }
@@ -1891,8 +1857,8 @@ static int kll_sketch_batch(dq_ctx* ctx, const dq_column* columns, int ncols, in
         const int nside = dq::ctx_side_streams(ctx, cstreams + 1, &fork_ev, join_ev);
         if (nside > 0) {
             nstreams = 1 + std::min(nside, ncols - 1);
-            KL_HIP(ctx, hipEventRecord(fork_ev, s));
-            for (int j = 1; j < nstreams; ++j) KL_HIP(ctx, hipStreamWaitEvent(cstreams[j], fork_ev, 0));
+            DQ_CTX_HIP(ctx, hipEventRecord(fork_ev, s));
+            for (int j = 1; j < nstreams; ++j) DQ_CTX_HIP(ctx, hipStreamWaitEvent(cstreams[j], fork_ev, 0));
         }
     }
     // dense level-0 streams go out while the host computes the (count-only) compaction schedules; batched: one launch
@@ -1900,25 +1866,25 @@ static int kll_sketch_batch(dq_ctx* ctx, const dq_column* columns, int ncols, in
         for (size_t j = 0; j < jobs.size(); ++j) {
             KColumnRun& r = run[job_col[j]];
             if (r.n <= 0) continue;
-            KL_HIP(ctx, buf.alloc((void**)&jobs[j].dense, (size_t)r.n * 8));
+            DQ_CTX_HIP(ctx, buf.alloc((void**)&jobs[j].dense, (size_t)r.n * 8));
             r.stream0 = jobs[j].dense;
         }
         KllCountJob* wjobs = nullptr;
-        KL_HIP(ctx, buf.alloc((void**)&wjobs, sizeof(KllCountJob) * jobs.size()));
-        KL_HIP(ctx, hipMemcpyAsync(wjobs, jobs.data(), sizeof(KllCountJob) * jobs.size(), hipMemcpyHostToDevice, s));
+        DQ_CTX_HIP(ctx, buf.alloc((void**)&wjobs, sizeof(KllCountJob) * jobs.size()));
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(wjobs, jobs.data(), sizeof(KllCountJob) * jobs.size(), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(kll_write_jobs_kernel, dim3((unsigned)ntiles, (unsigned)jobs.size()), dim3(kKllStageBlock), 0, s,
                            (const KllCountJob*)wjobs, nrows);
-        KL_HIP(ctx, hipGetLastError());
+        DQ_CTX_HIP(ctx, hipGetLastError());
     }
     for (int i = 0; i < ncols && !batched; ++i) {
         KColumnRun& r = run[i];
         if (r.zero_copy || r.n <= 0) continue;
         double* dense = nullptr;
-        KL_HIP(ctx, buf.alloc((void**)&dense, (size_t)r.n * 8));
+        DQ_CTX_HIP(ctx, buf.alloc((void**)&dense, (size_t)r.n * 8));
         hipLaunchKernelGGL(kll_write_kernel, dim3((unsigned)r.ntiles), dim3(kKllStageBlock), 0, cstreams[i % nstreams],
                            r.kc, nrows,
                            (const unsigned long long*)r.doffs, dense);
-        KL_HIP(ctx, hipGetLastError());
+        DQ_CTX_HIP(ctx, hipGetLastError());
         r.stream0 = dense;
     }
     const auto t0b = std::chrono::steady_clock::now();
@@ -1976,10 +1942,10 @@ static int kll_sketch_batch(dq_ctx* ctx, const dq_column* columns, int ncols, in
             }
         });
         uint8_t* gdev = nullptr;
-        KL_HIP(ctx, buf.alloc((void**)&gdev, seg_bytes + tab_bytes + mm_bytes));
+        DQ_CTX_HIP(ctx, buf.alloc((void**)&gdev, seg_bytes + tab_bytes + mm_bytes));
         // level 0 in place: (first row, end row) per descriptor, filled for level 0 by kll_locate_kernel
         unsigned long long* drows = nullptr;
-        if (inplace) KL_HIP(ctx, buf.alloc((void**)&drows, std::max<size_t>(nseg_all, 1) * 16));
+        if (inplace) DQ_CTX_HIP(ctx, buf.alloc((void**)&drows, std::max<size_t>(nseg_all, 1) * 16));
         std::vector<KllTail0Job> tail0;
         const uint64_t* dsegs = reinterpret_cast<const uint64_t*>(gdev);
         const KllColPtr* dtab = reinterpret_cast<const KllColPtr*>(gdev + seg_bytes);
@@ -2000,7 +1966,7 @@ static int kll_sketch_batch(dq_ctx* ctx, const dq_column* columns, int ncols, in
             const size_t tail_off = ((size_t)upper * 8 + 255) / 256 * 256;
             const size_t gat_off = tail_off + (nlev * sizeof(KllTail) + 255) / 256 * 256;
             uint8_t* scratch = nullptr;
-            KL_HIP(ctx, buf.alloc((void**)&scratch, gat_off + (size_t)r.ntail * 8 + 256));
+            DQ_CTX_HIP(ctx, buf.alloc((void**)&scratch, gat_off + (size_t)r.ntail * 8 + 256));
             double* dup = reinterpret_cast<double*>(scratch);
             dtails[i] = reinterpret_cast<KllTail*>(scratch + tail_off);
             dgats[i] = reinterpret_cast<double*>(scratch + gat_off);
@@ -2010,7 +1976,7 @@ static int kll_sketch_batch(dq_ctx* ctx, const dq_column* columns, int ncols, in
             const bool raw0 = r.stream0 == nullptr && r.n > 0;  // level 0 read in place
             double* tail0_buf = nullptr;
             if (raw0 && sc.levels[0].len > 0) {
-                KL_HIP(ctx, buf.alloc((void**)&tail0_buf, (size_t)sc.levels[0].len * 8));
+                DQ_CTX_HIP(ctx, buf.alloc((void**)&tail0_buf, (size_t)sc.levels[0].len * 8));
                 tail0.push_back(KllTail0Job{dtab + i, (unsigned long long)sc.levels[0].pos,
                                             (unsigned long long)sc.levels[0].len, tail0_buf});
             }
@@ -2026,7 +1992,7 @@ static int kll_sketch_batch(dq_ctx* ctx, const dq_column* columns, int ncols, in
                 at += (unsigned long long)l.len;
             }
         }
-        KL_HIP(ctx, hipMemcpyAsync(gdev, pin, seg_bytes + tab_bytes + mm_bytes, hipMemcpyHostToDevice, s));
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(gdev, pin, seg_bytes + tab_bytes + mm_bytes, hipMemcpyHostToDevice, s));
         if (inplace) {
             // level 0's descriptors are the first NC * ncols groups (level-major): their row ranges, then the final
             // level-0 buffers of the columns read in place
@@ -2036,11 +2002,11 @@ static int kll_sketch_batch(dq_ctx* ctx, const dq_column* columns, int ncols, in
                                    dtab, drows);
             if (!tail0.empty()) {
                 KllTail0Job* dt0 = nullptr;
-                KL_HIP(ctx, buf.alloc((void**)&dt0, tail0.size() * sizeof(KllTail0Job)));
-                KL_HIP(ctx, hipMemcpyAsync(dt0, tail0.data(), tail0.size() * sizeof(KllTail0Job), hipMemcpyHostToDevice, s));
+                DQ_CTX_HIP(ctx, buf.alloc((void**)&dt0, tail0.size() * sizeof(KllTail0Job)));
+                DQ_CTX_HIP(ctx, hipMemcpyAsync(dt0, tail0.data(), tail0.size() * sizeof(KllTail0Job), hipMemcpyHostToDevice, s));
                 hipLaunchKernelGGL(kll_tail0_kernel, dim3((unsigned)tail0.size()), dim3(256), 0, s, (const KllTail0Job*)dt0);
             }
-            KL_HIP(ctx, hipGetLastError());
+            DQ_CTX_HIP(ctx, hipGetLastError());
         }
         for (size_t h = 0; h < maxlev; ++h)
             for (size_t c = 0; c < NC; ++c) {
@@ -2055,13 +2021,13 @@ static int kll_sketch_batch(dq_ctx* ctx, const dq_column* columns, int ncols, in
         for (int i = 0; i < ncols; ++i) {
             KColumnRun& r = run[i];
             const size_t nlev = r.sc.levels.size();
-            KL_HIP(ctx, hipMemcpyAsync(dtails[i], pin + r.pin_at, nlev * sizeof(KllTail), hipMemcpyHostToDevice, s));
+            DQ_CTX_HIP(ctx, hipMemcpyAsync(dtails[i], pin + r.pin_at, nlev * sizeof(KllTail), hipMemcpyHostToDevice, s));
             if (r.ntail)
                 hipLaunchKernelGGL(kll_gather_kernel, dim3((unsigned)nlev), dim3(256), 0, s, (const KllTail*)dtails[i], dgats[i]);
-            KL_HIP(ctx, hipGetLastError());
+            DQ_CTX_HIP(ctx, hipGetLastError());
             if (r.ntail)
-                KL_HIP(ctx, hipMemcpyAsync(r.hgat, dgats[i], sizeof(double) * (size_t)r.ntail, hipMemcpyDeviceToHost, s));
-            KL_HIP(ctx, hipMemcpyAsync(r.hgat + r.ntail, dmm + 2 * i, 16, hipMemcpyDeviceToHost, s));
+                DQ_CTX_HIP(ctx, hipMemcpyAsync(r.hgat, dgats[i], sizeof(double) * (size_t)r.ntail, hipMemcpyDeviceToHost, s));
+            DQ_CTX_HIP(ctx, hipMemcpyAsync(r.hgat + r.ntail, dmm + 2 * i, 16, hipMemcpyDeviceToHost, s));
         }
     } else {
         // pinned staging for every column: [segment descriptors][level tails][gathered final buffers + min / max keys]
@@ -2113,7 +2079,7 @@ static int kll_sketch_batch(dq_ctx* ctx, const dq_column* columns, int ncols, in
             const size_t tail_off = mm_off + 256;
             const size_t gat_off = tail_off + (nlev * sizeof(KllTail) + 255) / 256 * 256;
             uint8_t* scratch = nullptr;
-            KL_HIP(ctx, buf.alloc((void**)&scratch, gat_off + (size_t)r.ntail * 8 + 256));
+            DQ_CTX_HIP(ctx, buf.alloc((void**)&scratch, gat_off + (size_t)r.ntail * 8 + 256));
             double* dup = reinterpret_cast<double*>(scratch);
             uint64_t* dsegs = reinterpret_cast<uint64_t*>(scratch + seg_off);
             unsigned long long* dminmax = reinterpret_cast<unsigned long long*>(scratch + mm_off);
@@ -2125,8 +2091,8 @@ static int kll_sketch_batch(dq_ctx* ctx, const dq_column* columns, int ncols, in
 
             // one launch per (level, kernel class) group; the order inside a level is free because every compaction's
             // input range and output slot are explicit
-            if (nseg_all) KL_HIP(ctx, hipMemcpyAsync(dsegs, hsegs, nseg_all * 8, hipMemcpyHostToDevice, cs));
-            KL_HIP(ctx, hipMemcpyAsync(dminmax, mm_init, sizeof(mm_init), hipMemcpyHostToDevice, cs));
+            if (nseg_all) DQ_CTX_HIP(ctx, hipMemcpyAsync(dsegs, hsegs, nseg_all * 8, hipMemcpyHostToDevice, cs));
+            DQ_CTX_HIP(ctx, hipMemcpyAsync(dminmax, mm_init, sizeof(mm_init), hipMemcpyHostToDevice, cs));
             for (const KColumnRun::Launch& L : r.launches) {  // a level that compacted always has a level above it
                 const size_t h = L.level;
                 const double* src = h == 0 ? r.stream0 : dup + r.lbase[h];
@@ -2142,19 +2108,19 @@ static int kll_sketch_batch(dq_ctx* ctx, const dq_column* columns, int ncols, in
                 htails[h] = KllTail{(unsigned long long)(uintptr_t)src, (unsigned long long)l.len, at};
                 at += (unsigned long long)l.len;
             }
-            KL_HIP(ctx, hipMemcpyAsync(dtails, htails, nlev * sizeof(KllTail), hipMemcpyHostToDevice, cs));
+            DQ_CTX_HIP(ctx, hipMemcpyAsync(dtails, htails, nlev * sizeof(KllTail), hipMemcpyHostToDevice, cs));
             if (r.ntail) hipLaunchKernelGGL(kll_gather_kernel, dim3((unsigned)nlev), dim3(256), 0, cs, (const KllTail*)dtails, dgat);
-            KL_HIP(ctx, hipGetLastError());
-            if (r.ntail) KL_HIP(ctx, hipMemcpyAsync(r.hgat, dgat, sizeof(double) * (size_t)r.ntail, hipMemcpyDeviceToHost, cs));
-            KL_HIP(ctx, hipMemcpyAsync(r.hgat + r.ntail, dminmax, 16, hipMemcpyDeviceToHost, cs));
+            DQ_CTX_HIP(ctx, hipGetLastError());
+            if (r.ntail) DQ_CTX_HIP(ctx, hipMemcpyAsync(r.hgat, dgat, sizeof(double) * (size_t)r.ntail, hipMemcpyDeviceToHost, cs));
+            DQ_CTX_HIP(ctx, hipMemcpyAsync(r.hgat + r.ntail, dminmax, 16, hipMemcpyDeviceToHost, cs));
         }
     }
     for (int j = 1; j < nstreams; ++j) {
-        KL_HIP(ctx, hipEventRecord(join_ev[j - 1], cstreams[j]));
-        KL_HIP(ctx, hipStreamWaitEvent(s, join_ev[j - 1], 0));
+        DQ_CTX_HIP(ctx, hipEventRecord(join_ev[j - 1], cstreams[j]));
+        DQ_CTX_HIP(ctx, hipStreamWaitEvent(s, join_ev[j - 1], 0));
     }
     const auto t2 = std::chrono::steady_clock::now();
-    KL_HIP(ctx, hipStreamSynchronize(s));
+    DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
     if (getenv("DQ_KLL_TIMING")) {
         auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
             return std::chrono::duration<double, std::milli>(b - a).count();

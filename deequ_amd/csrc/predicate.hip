@@ -11,6 +11,7 @@
 #include <math.h>
 
 #include "dq_common.h"
+#include "dq_device.h"
 #include "dq_internal.h"
 #include "dq_parse.h"
 #include "java_dtoa.h"
@@ -286,12 +287,6 @@ __device__ bool like_match_xf(const uint8_t* s, int ns, int xf, const uint8_t* p
     return pi == np;
 }
 
-__device__ __forceinline__ int utf8_chars(const uint8_t* s, int n) {
-    int c = 0;
-    for (int i = 0; i < n; ++i) c += (s[i] & 0xC0) != 0x80;
-    return c;
-}
-
 __device__ Val load_col(const PredColumn& c, int64_t row) {
     if (c.validity) {
         const uint8_t* vb = reinterpret_cast<const uint8_t*>(c.validity);
@@ -545,13 +540,8 @@ predicate_kernel(const PredProgram* __restrict__ progp, const PredColumn* __rest
                     if (a.null) break;
                     if (RX) {
                         const dq_const k = prog.consts[arg];
-                        const int32_t* image = reinterpret_cast<const int32_t*>(prog.strings + k.str_offset);
-                        rx::RxProg rp;
-                        rp.ninstr = image[1];
-                        rp.anchored = image[6];
-                        rp.ins = image + 8;
-                        rp.classes = rp.ins + 3 * rp.ninstr;
-                        rp.ranges = rp.classes + 2 * image[2];
+                        const rx::RxProg rp =
+                            rx::rx_program(reinterpret_cast<const int32_t*>(prog.strings + k.str_offset));
                         uint8_t buf[40];
                         const uint8_t* sv = a.s;
                         int n = a.slen, xf = a.xf;
@@ -561,23 +551,10 @@ predicate_kernel(const PredProgram* __restrict__ progp, const PredColumn* __rest
                             xf = 0;
                         }
                         uint64_t stk[rx::kRxStack];
-                        bool found = false;
-                        for (int start = 0; start <= n;) {
-                            const int end = rx::rx_match_at(rp, sv, n, start, stk, xf);
-                            if (end == -2) {
-                                atomicOr(status, 1);
-                                break;
-                            }
-                            if (end >= 0) {
-                                found = true;
-                                break;
-                            }
-                            if (rp.anchored || start == n) break;
-                            int len;
-                            rx::decode(sv, n, start, len);
-                            start += len;
-                        }
-                        st[sp - 1] = vbool(found);
+                        int start;
+                        const int end = rx::rx_find(rp, sv, n, stk, start, xf);
+                        if (end == -2) atomicOr(status, 1);
+                        st[sp - 1] = vbool(end >= 0);
                     }
                     st_type[sp - 1] = 0;
                     break;

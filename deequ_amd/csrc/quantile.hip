@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "dq_common.h"
+#include "dq_device.h"
 #include "dq_internal.h"
 
 namespace dq {
@@ -67,10 +68,6 @@ struct QColumn {
     int32_t decimal_scale;  // DECIMAL: value = unscaled / 10^scale (Spark Decimal.toDouble, compact form)
     double pow10;
 };
-
-__device__ __forceinline__ bool q_valid(const QColumn& c, int64_t r) {
-    return c.validity == nullptr || ((c.validity[r >> 6] >> (r & 63)) & 1ull);
-}
 
 __device__ __forceinline__ double q_load(const QColumn& c, int64_t r) {
     switch (c.elem) {
@@ -146,7 +143,7 @@ __global__ void q_sample_kernel(QColumn c, int64_t nrows, uint64_t* __restrict__
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= kQSample) return;
     const int64_t r = (int64_t)(((uint64_t)(2 * i + 1) * (uint64_t)nrows) / (2 * kQSample));  // nrows < 2^46
-    const bool v = r < nrows && q_valid(c, r);
+    const bool v = r < nrows && row_valid(c.validity, r);
     ok[i] = v ? 1 : 0;
     keys[i] = v ? order_key(q_load(c, r)) : 0;
 }
@@ -307,7 +304,7 @@ q_sample_multi_kernel(const QPart* __restrict__ parts, const int32_t* __restrict
         int p = part_begin[r];
         while (p + 1 < part_begin[r + 1] && g >= parts[p + 1].row0) ++p;
         const int64_t lr = g - parts[p].row0;
-        if (lr >= 0 && lr < parts[p].nrows && q_valid(parts[p].qc, lr)) {
+        if (lr >= 0 && lr < parts[p].nrows && row_valid(parts[p].qc.validity, lr)) {
             v = true;
             key = order_key(q_load(parts[p].qc, lr));
         }
@@ -485,13 +482,6 @@ __global__ void q_gather_kernel(const uint64_t* __restrict__ sorted, const int64
         default: { constexpr int E = ET_U8; BODY; } break;       \
     }
 
-hipStream_t ctx_stream(dq_ctx* ctx);
-int ctx_device(dq_ctx* ctx);
-int ctx_fail(dq_ctx* ctx, int code, const char* msg);
-int ctx_cus(dq_ctx* ctx);
-int ctx_num_subs(dq_ctx* ctx);      // devices of a multi-device context, 0 for a single-device one
-dq_ctx* ctx_sub(dq_ctx* ctx, int i);
-
 }  // namespace dq
 
 namespace {
@@ -506,42 +496,6 @@ double host_key_value(uint64_t k) {
     return d;
 }
 
-// Device buffers released on every exit path.
-// Device buffers released on every exit path: from the context's scratch cache when `ctx` is set (a one-device
-// context: a hipFree waits for the whole device, stalling this call behind other contexts' kernels), else hipMalloc.
-struct QBuffers {
-    dq_ctx* ctx = nullptr;
-    std::vector<std::pair<void*, size_t>> ptrs;
-    ~QBuffers() {
-        for (const auto& p : ptrs) {
-            if (ctx) dq::scratch_release(ctx, p.first, p.second);
-            else (void)hipFree(p.first);
-        }
-    }
-    hipError_t alloc(void** p, size_t bytes) {
-        bytes = std::max<size_t>(bytes, 16);
-        if (ctx) {
-            *p = dq::scratch_alloc(ctx, bytes);
-            if (!*p) return hipErrorOutOfMemory;
-        } else {
-            hipError_t e = hipMalloc(p, bytes);
-            if (e != hipSuccess) return e;
-        }
-        ptrs.push_back({*p, bytes});
-        return hipSuccess;
-    }
-};
-
-}  // namespace
-
-#define QT_HIP(ctx, expr)                                                                         \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return dq::ctx_fail((ctx), DQ_ERR_DEVICE, hipGetErrorString(e_));   \
-    } while (0)
-
-namespace {
-
 // One shard of the column on one device: the whole column on a single-device context, one contiguous row range per
 // device on a multi-device one (dq_open_devices). Every pass runs per shard on its own device and stream; the host
 // adds the shards' histograms, so the order statistics are those of the whole column for any device count.
@@ -549,7 +503,7 @@ struct QShard {
     dq_ctx* ctx = nullptr;
     QColumn qc;
     int64_t nrows = 0;
-    QBuffers buf;
+    ScratchBuffers buf{nullptr};  // the scratch cache on a one-device context (set below), else hipMalloc
     uint64_t* dkeys = nullptr;
     uint8_t* dok = nullptr;
     uint64_t* dspl = nullptr;
@@ -607,12 +561,6 @@ hipError_t q_stage_and_sample(QShard& sh, const dq_column& col) {
 }
 
 }  // namespace
-
-#define QS_HIP(ctx, expr)                                                                                  \
-    do {                                                                                                   \
-        hipError_t e_ = (expr);                                                                            \
-        if (e_ != hipSuccess) return dq::ctx_fail((ctx), DQ_ERR_DEVICE, hipGetErrorString(e_));            \
-    } while (0)
 
 extern "C" {
 
@@ -678,27 +626,27 @@ int64_t dq_quantile_summary(dq_ctx* ctx, const dq_column* column, int64_t nrows,
     // ---- 2. histogram per shard, added on the host ------------------------------------------------
     for (QShard& q : sh) {
         if (!q.nrows) continue;
-        QS_HIP(ctx, hipSetDevice(dq::ctx_device(q.ctx)));
+        DQ_CTX_HIP(ctx, hipSetDevice(dq::ctx_device(q.ctx)));
         hipStream_t s = dq::ctx_stream(q.ctx);
-        QS_HIP(ctx, q.buf.alloc((void**)&q.dspl, sizeof(uint64_t) * kQBuckets));
-        QS_HIP(ctx, hipMemcpyAsync(q.dspl, tree.data(), sizeof(uint64_t) * kQBuckets, hipMemcpyHostToDevice, s));
-        QS_HIP(ctx, q.buf.alloc((void**)&q.dhist, sizeof(unsigned long long) * kQBuckets * 2));
-        QS_HIP(ctx, hipMemsetAsync(q.dhist, 0, sizeof(unsigned long long) * kQBuckets * 2, s));
+        DQ_CTX_HIP(ctx, q.buf.alloc((void**)&q.dspl, sizeof(uint64_t) * kQBuckets));
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(q.dspl, tree.data(), sizeof(uint64_t) * kQBuckets, hipMemcpyHostToDevice, s));
+        DQ_CTX_HIP(ctx, q.buf.alloc((void**)&q.dhist, sizeof(unsigned long long) * kQBuckets * 2));
+        DQ_CTX_HIP(ctx, hipMemsetAsync(q.dhist, 0, sizeof(unsigned long long) * kQBuckets * 2, s));
         const int64_t lanes_needed = (q.nrows + kQRowsPerLane - 1) / kQRowsPerLane;
         q.grid = (int)std::max<int64_t>(1, std::min<int64_t>((lanes_needed + kQBlock - 1) / kQBlock,
                                                              (int64_t)dq::ctx_cus(q.ctx) * 2));
         Q_ET_DISPATCH(q.qc.elem, hipLaunchKernelGGL(q_hist_kernel<E>, dim3(q.grid), dim3(kQBlock), 0, s, q.qc, q.nrows,
                                                     (const uint64_t*)q.dspl, q.dhist, q.dhist + kQBuckets));
-        QS_HIP(ctx, hipGetLastError());
+        DQ_CTX_HIP(ctx, hipGetLastError());
         q.hist.assign(kQBuckets * 2, 0);
-        QS_HIP(ctx, hipMemcpyAsync(q.hist.data(), q.dhist, sizeof(unsigned long long) * kQBuckets * 2,
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(q.hist.data(), q.dhist, sizeof(unsigned long long) * kQBuckets * 2,
                                    hipMemcpyDeviceToHost, s));
     }
     std::vector<unsigned long long> hist(kQBuckets * 2, 0);
     for (QShard& q : sh) {
         if (!q.nrows) continue;
-        QS_HIP(ctx, hipSetDevice(dq::ctx_device(q.ctx)));
-        QS_HIP(ctx, hipStreamSynchronize(dq::ctx_stream(q.ctx)));
+        DQ_CTX_HIP(ctx, hipSetDevice(dq::ctx_device(q.ctx)));
+        DQ_CTX_HIP(ctx, hipStreamSynchronize(dq::ctx_stream(q.ctx)));
         for (int b = 0; b < kQBuckets * 2; ++b) hist[b] += q.hist[b];
     }
     const unsigned long long* eq = hist.data() + kQBuckets;
@@ -755,9 +703,9 @@ int64_t dq_quantile_summary(dq_ctx* ctx, const dq_column* column, int64_t nrows,
     // ---- 4. compaction per shard, candidates gathered on the first shard's device ------------------
     QShard& s0 = sh[0];
     uint64_t *dall = nullptr, *dsorted = nullptr;
-    QS_HIP(ctx, hipSetDevice(dq::ctx_device(s0.ctx)));
-    QS_HIP(ctx, s0.buf.alloc((void**)&dall, sizeof(uint64_t) * ncand));
-    QS_HIP(ctx, s0.buf.alloc((void**)&dsorted, sizeof(uint64_t) * ncand));
+    DQ_CTX_HIP(ctx, hipSetDevice(dq::ctx_device(s0.ctx)));
+    DQ_CTX_HIP(ctx, s0.buf.alloc((void**)&dall, sizeof(uint64_t) * ncand));
+    DQ_CTX_HIP(ctx, s0.buf.alloc((void**)&dsorted, sizeof(uint64_t) * ncand));
     int64_t at = 0;
     for (QShard& q : sh) {
         if (!q.nrows) continue;
@@ -770,36 +718,36 @@ int64_t dq_quantile_summary(dq_ctx* ctx, const dq_column* column, int64_t nrows,
         }
         q.ncand = nloc;
         if (nloc == 0) continue;
-        QS_HIP(ctx, hipSetDevice(dq::ctx_device(q.ctx)));
+        DQ_CTX_HIP(ctx, hipSetDevice(dq::ctx_device(q.ctx)));
         hipStream_t s = dq::ctx_stream(q.ctx);
-        QS_HIP(ctx, q.buf.alloc((void**)&q.dtarget, sizeof(uint32_t) * kQBuckets));
-        QS_HIP(ctx, q.buf.alloc((void**)&q.dcursor, sizeof(unsigned long long) * kQBuckets));
-        QS_HIP(ctx, q.buf.alloc((void**)&q.dcand, sizeof(uint64_t) * nloc));
-        QS_HIP(ctx, hipMemcpyAsync(q.dtarget, target.data(), sizeof(uint32_t) * kQBuckets, hipMemcpyHostToDevice, s));
-        QS_HIP(ctx, hipMemcpyAsync(q.dcursor, lcur.data(), sizeof(unsigned long long) * kQBuckets, hipMemcpyHostToDevice, s));
+        DQ_CTX_HIP(ctx, q.buf.alloc((void**)&q.dtarget, sizeof(uint32_t) * kQBuckets));
+        DQ_CTX_HIP(ctx, q.buf.alloc((void**)&q.dcursor, sizeof(unsigned long long) * kQBuckets));
+        DQ_CTX_HIP(ctx, q.buf.alloc((void**)&q.dcand, sizeof(uint64_t) * nloc));
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(q.dtarget, target.data(), sizeof(uint32_t) * kQBuckets, hipMemcpyHostToDevice, s));
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(q.dcursor, lcur.data(), sizeof(unsigned long long) * kQBuckets, hipMemcpyHostToDevice, s));
         Q_ET_DISPATCH(q.qc.elem, hipLaunchKernelGGL(q_compact_kernel<E>, dim3(q.grid), dim3(kQBlock), 0, s, q.qc,
                                                     q.nrows, (const uint64_t*)q.dspl, (const uint32_t*)q.dtarget,
                                                     q.dcursor, q.dcand));
-        QS_HIP(ctx, hipGetLastError());
-        QS_HIP(ctx, hipMemcpyPeerAsync(dall + at, dq::ctx_device(s0.ctx), q.dcand, dq::ctx_device(q.ctx),
+        DQ_CTX_HIP(ctx, hipGetLastError());
+        DQ_CTX_HIP(ctx, hipMemcpyPeerAsync(dall + at, dq::ctx_device(s0.ctx), q.dcand, dq::ctx_device(q.ctx),
                                        sizeof(uint64_t) * nloc, s));
         at += nloc;
     }
     for (QShard& q : sh) {
         if (!q.ncand) continue;
-        QS_HIP(ctx, hipSetDevice(dq::ctx_device(q.ctx)));
-        QS_HIP(ctx, hipStreamSynchronize(dq::ctx_stream(q.ctx)));
+        DQ_CTX_HIP(ctx, hipSetDevice(dq::ctx_device(q.ctx)));
+        DQ_CTX_HIP(ctx, hipStreamSynchronize(dq::ctx_stream(q.ctx)));
     }
     if (at != ncand) return dq::ctx_fail(ctx, DQ_ERR_DEVICE, "dq_quantile_summary: candidate count mismatch");
 
     // ---- 5. sort all candidates (bucket segments follow key order) --------------------------------
-    QS_HIP(ctx, hipSetDevice(dq::ctx_device(s0.ctx)));
+    DQ_CTX_HIP(ctx, hipSetDevice(dq::ctx_device(s0.ctx)));
     hipStream_t s = dq::ctx_stream(s0.ctx);
     size_t tmp_bytes = 0;
-    QS_HIP(ctx, rocprim::radix_sort_keys(nullptr, tmp_bytes, dall, dsorted, (size_t)ncand, 0, 64, s));
+    DQ_CTX_HIP(ctx, rocprim::radix_sort_keys(nullptr, tmp_bytes, dall, dsorted, (size_t)ncand, 0, 64, s));
     void* dtmp = nullptr;
-    QS_HIP(ctx, s0.buf.alloc(&dtmp, tmp_bytes));
-    QS_HIP(ctx, rocprim::radix_sort_keys(dtmp, tmp_bytes, dall, dsorted, (size_t)ncand, 0, 64, s));
+    DQ_CTX_HIP(ctx, s0.buf.alloc(&dtmp, tmp_bytes));
+    DQ_CTX_HIP(ctx, rocprim::radix_sort_keys(dtmp, tmp_bytes, dall, dsorted, (size_t)ncand, 0, 64, s));
 
     // ---- 6. gather -------------------------------------------------------------------------------
     std::vector<int64_t> idx;
@@ -812,15 +760,15 @@ int64_t dq_quantile_summary(dq_ctx* ctx, const dq_column* column, int64_t nrows,
     const int ng = (int)idx.size();
     int64_t* didx = nullptr;
     double* dvals = nullptr;
-    QS_HIP(ctx, s0.buf.alloc((void**)&didx, sizeof(int64_t) * ng));
-    QS_HIP(ctx, s0.buf.alloc((void**)&dvals, sizeof(double) * ng));
-    QS_HIP(ctx, hipMemcpyAsync(didx, idx.data(), sizeof(int64_t) * ng, hipMemcpyHostToDevice, s));
+    DQ_CTX_HIP(ctx, s0.buf.alloc((void**)&didx, sizeof(int64_t) * ng));
+    DQ_CTX_HIP(ctx, s0.buf.alloc((void**)&dvals, sizeof(double) * ng));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(didx, idx.data(), sizeof(int64_t) * ng, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(q_gather_kernel, dim3((ng + 255) / 256), dim3(256), 0, s, (const uint64_t*)dsorted,
                        (const int64_t*)didx, ng, dvals);
-    QS_HIP(ctx, hipGetLastError());
+    DQ_CTX_HIP(ctx, hipGetLastError());
     std::vector<double> got(ng);
-    QS_HIP(ctx, hipMemcpyAsync(got.data(), dvals, sizeof(double) * ng, hipMemcpyDeviceToHost, s));
-    QS_HIP(ctx, hipStreamSynchronize(s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(got.data(), dvals, sizeof(double) * ng, hipMemcpyDeviceToHost, s));
+    DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
     for (int j = 0; j < ng; ++j) values_out[which[j]] = got[j];
     return ns;
 }
@@ -871,26 +819,15 @@ int dq_quantile_summaries(dq_ctx* ctx, const dq_column* parts, const int32_t* pa
         }
         return 0;
     }
-    QS_HIP(ctx, hipSetDevice(dq::ctx_device(ctx)));
+    DQ_CTX_HIP(ctx, hipSetDevice(dq::ctx_device(ctx)));
     hipStream_t s = dq::ctx_stream(ctx);
 
     // scratch blocks handed back to the context's cache on every exit path (their last use is on `s`)
-    struct Scratch {
-        dq_ctx* ctx;
-        std::vector<std::pair<void*, size_t>> blocks;
-        ~Scratch() {
-            for (auto& b : blocks) dq::scratch_release(ctx, b.first, b.second);
-        }
-        void* get(size_t bytes) {
-            void* p = dq::scratch_alloc(ctx, bytes);
-            if (p) blocks.emplace_back(p, bytes);
-            return p;
-        }
-    } scr{ctx, {}};
+    dq::ScratchBuffers scr(ctx);
 #define QM_ALLOC(ptr, T, count)                                                                          \
     do {                                                                                                 \
-        (ptr) = (T*)scr.get(sizeof(T) * (size_t)std::max<int64_t>((count), 1));                          \
-        if (!(ptr)) return dq::ctx_fail(ctx, DQ_ERR_DEVICE, "dq_quantile_summaries: out of device memory"); \
+        if (scr.alloc((void**)&(ptr), sizeof(T) * (size_t)std::max<int64_t>((count), 1)) != hipSuccess)  \
+            return dq::ctx_fail(ctx, DQ_ERR_DEVICE, "dq_quantile_summaries: out of device memory");     \
     } while (0)
 
     // ---- part table (host parts staged into scratch) ------------------------------------------------
@@ -917,15 +854,15 @@ int dq_quantile_summaries(dq_ctx* ctx, const dq_column* parts, const int32_t* pa
             } else if (c.length > 0) {
                 const size_t vbytes = (size_t)c.length * elem_size(q.qc.elem);
                 const size_t bbytes = (size_t)(c.length + 63) / 64 * 8;
-                void* v = scr.get(vbytes);
-                if (!v) return dq::ctx_fail(ctx, DQ_ERR_DEVICE, "dq_quantile_summaries: out of device memory");
-                QS_HIP(ctx, hipMemcpyAsync(v, c.values, vbytes, hipMemcpyHostToDevice, s));
+                void* v;
+                QM_ALLOC(v, uint8_t, vbytes);
+                DQ_CTX_HIP(ctx, hipMemcpyAsync(v, c.values, vbytes, hipMemcpyHostToDevice, s));
                 q.qc.values = v;
                 if (c.validity) {
-                    void* m = scr.get(bbytes);
-                    if (!m) return dq::ctx_fail(ctx, DQ_ERR_DEVICE, "dq_quantile_summaries: out of device memory");
-                    QS_HIP(ctx, hipMemsetAsync(m, 0, bbytes, s));
-                    QS_HIP(ctx, hipMemcpyAsync(m, c.validity, (size_t)(c.length + 7) / 8, hipMemcpyHostToDevice, s));
+                    void* m;
+                    QM_ALLOC(m, uint8_t, bbytes);
+                    DQ_CTX_HIP(ctx, hipMemsetAsync(m, 0, bbytes, s));
+                    DQ_CTX_HIP(ctx, hipMemcpyAsync(m, c.validity, (size_t)(c.length + 7) / 8, hipMemcpyHostToDevice, s));
                     q.qc.validity = (const uint64_t*)m;
                 }
             }
@@ -949,31 +886,31 @@ int dq_quantile_summaries(dq_ctx* ctx, const dq_column* parts, const int32_t* pa
     QM_ALLOC(dtree, uint64_t, (int64_t)nreq * kQBuckets);
     QM_ALLOC(dvalid, unsigned int, nreq);
     QM_ALLOC(dhist, unsigned long long, (int64_t)nreq * 2 * kQBuckets);
-    QS_HIP(ctx, hipMemcpyAsync(dparts, qp.data(), sizeof(QPart) * nparts, hipMemcpyHostToDevice, s));
-    QS_HIP(ctx, hipMemcpyAsync(dbegin, part_begin, sizeof(int32_t) * (nreq + 1), hipMemcpyHostToDevice, s));
-    QS_HIP(ctx, hipMemcpyAsync(drows, req_rows.data(), sizeof(int64_t) * nreq, hipMemcpyHostToDevice, s));
-    QS_HIP(ctx, hipMemsetAsync(dvalid, 0, sizeof(unsigned int) * nreq, s));
-    QS_HIP(ctx, hipMemsetAsync(dhist, 0, sizeof(unsigned long long) * nreq * 2 * kQBuckets, s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(dparts, qp.data(), sizeof(QPart) * nparts, hipMemcpyHostToDevice, s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(dbegin, part_begin, sizeof(int32_t) * (nreq + 1), hipMemcpyHostToDevice, s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(drows, req_rows.data(), sizeof(int64_t) * nreq, hipMemcpyHostToDevice, s));
+    DQ_CTX_HIP(ctx, hipMemsetAsync(dvalid, 0, sizeof(unsigned int) * nreq, s));
+    DQ_CTX_HIP(ctx, hipMemsetAsync(dhist, 0, sizeof(unsigned long long) * nreq * 2 * kQBuckets, s));
 
     // ---- 1. samples, their per-request sort, splitters: all on the device ----------------------------
     hipLaunchKernelGGL(q_sample_multi_kernel, dim3(kQSample / 256, nreq), dim3(256), 0, s, (const QPart*)dparts,
                        (const int32_t*)dbegin, (const int64_t*)drows, dkeys, dvalid);
-    QS_HIP(ctx, hipGetLastError());
+    DQ_CTX_HIP(ctx, hipGetLastError());
     std::vector<unsigned int> seg_off(nreq + 1);
     for (int r = 0; r <= nreq; ++r) seg_off[r] = (unsigned int)r * kQSample;
     unsigned int* dseg;
     QM_ALLOC(dseg, unsigned int, nreq + 1);
-    QS_HIP(ctx, hipMemcpyAsync(dseg, seg_off.data(), sizeof(unsigned int) * (nreq + 1), hipMemcpyHostToDevice, s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(dseg, seg_off.data(), sizeof(unsigned int) * (nreq + 1), hipMemcpyHostToDevice, s));
     size_t tmp_bytes = 0;
-    QS_HIP(ctx, rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, dkeys, dsorted, (unsigned int)nreq * kQSample,
+    DQ_CTX_HIP(ctx, rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, dkeys, dsorted, (unsigned int)nreq * kQSample,
                                                    (unsigned int)nreq, dseg, dseg + 1, 0, 64, s));
-    void* dtmp = scr.get(tmp_bytes);
-    if (!dtmp) return dq::ctx_fail(ctx, DQ_ERR_DEVICE, "dq_quantile_summaries: out of device memory");
-    QS_HIP(ctx, rocprim::segmented_radix_sort_keys(dtmp, tmp_bytes, dkeys, dsorted, (unsigned int)nreq * kQSample,
+    void* dtmp;
+    QM_ALLOC(dtmp, uint8_t, tmp_bytes);
+    DQ_CTX_HIP(ctx, rocprim::segmented_radix_sort_keys(dtmp, tmp_bytes, dkeys, dsorted, (unsigned int)nreq * kQSample,
                                                    (unsigned int)nreq, dseg, dseg + 1, 0, 64, s));
     hipLaunchKernelGGL(q_splitters_kernel, dim3(nreq), dim3(256), 0, s, (const uint64_t*)dsorted,
                        (const unsigned int*)dvalid, dspl, dtree);
-    QS_HIP(ctx, hipGetLastError());
+    DQ_CTX_HIP(ctx, hipGetLastError());
 
     // ---- 2. histograms of every part ------------------------------------------------------------------
     int64_t max_part = 1;
@@ -991,7 +928,7 @@ int dq_quantile_summaries(dq_ctx* ctx, const dq_column* parts, const int32_t* pa
     std::stable_sort(typed.begin(), typed.end(), [](const QPart& a, const QPart& b) { return a.qc.elem < b.qc.elem; });
     QPart* dtyped;
     QM_ALLOC(dtyped, QPart, nparts);
-    QS_HIP(ctx, hipMemcpyAsync(dtyped, typed.data(), sizeof(QPart) * nparts, hipMemcpyHostToDevice, s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(dtyped, typed.data(), sizeof(QPart) * nparts, hipMemcpyHostToDevice, s));
     std::vector<std::pair<int, int>> type_runs;  // (first typed part, count)
     for (int i = 0; i < nparts;) {
         int j = i;
@@ -1000,18 +937,19 @@ int dq_quantile_summaries(dq_ctx* ctx, const dq_column* parts, const int32_t* pa
         i = j;
     }
     // every row's bucket id (2 B a row) for the compaction; without room for it the compaction searches again
-    uint16_t* dbid = getenv("DQ_Q_NO_BID") ? nullptr : (uint16_t*)scr.get(sizeof(uint16_t) * (size_t)std::max<int64_t>(total_rows, 1));
+    uint16_t* dbid = nullptr;
+    if (!getenv("DQ_Q_NO_BID")) (void)scr.alloc((void**)&dbid, sizeof(uint16_t) * (size_t)total_rows);
     for (auto& tr : type_runs) {
         Q_ET_DISPATCH(typed[tr.first].qc.elem,
                       hipLaunchKernelGGL(q_hist_multi_kernel<E>, dim3(gx, tr.second), dim3(kQHistBlock), 0, s,
                                          (const QPart*)(dtyped + tr.first), (const uint64_t*)dtree, dhist, dbid));
-        QS_HIP(ctx, hipGetLastError());
+        DQ_CTX_HIP(ctx, hipGetLastError());
     }
     std::vector<unsigned long long> hist((size_t)nreq * 2 * kQBuckets);
     std::vector<uint64_t> spl((size_t)nreq * kQBuckets);
-    QS_HIP(ctx, hipMemcpyAsync(hist.data(), dhist, sizeof(unsigned long long) * hist.size(), hipMemcpyDeviceToHost, s));
-    QS_HIP(ctx, hipMemcpyAsync(spl.data(), dspl, sizeof(uint64_t) * spl.size(), hipMemcpyDeviceToHost, s));
-    QS_HIP(ctx, hipStreamSynchronize(s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(hist.data(), dhist, sizeof(unsigned long long) * hist.size(), hipMemcpyDeviceToHost, s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(spl.data(), dspl, sizeof(uint64_t) * spl.size(), hipMemcpyDeviceToHost, s));
+    DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
 
     // ---- 3. ranks -> (bucket, residual); target buckets get absolute candidate segments -----------------
     constexpr int64_t kSelectMaxRanks = 4096;  // more ranks than this (relative_error 0 on small data): sort instead
@@ -1103,8 +1041,8 @@ int dq_quantile_summaries(dq_ctx* ctx, const dq_column* parts, const int32_t* pa
     QM_ALLOC(dtarget, uint32_t, (int64_t)nreq * kQBuckets);
     QM_ALLOC(dcursor, unsigned long long, (int64_t)nreq * kQBuckets);
     QM_ALLOC(dcand, uint64_t, ncand);
-    QS_HIP(ctx, hipMemcpyAsync(dtarget, target.data(), sizeof(uint32_t) * target.size(), hipMemcpyHostToDevice, s));
-    QS_HIP(ctx, hipMemcpyAsync(dcursor, cursor.data(), sizeof(unsigned long long) * cursor.size(), hipMemcpyHostToDevice, s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(dtarget, target.data(), sizeof(uint32_t) * target.size(), hipMemcpyHostToDevice, s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(dcursor, cursor.data(), sizeof(unsigned long long) * cursor.size(), hipMemcpyHostToDevice, s));
     for (auto& tr : type_runs) {
         if (dbid)
             Q_ET_DISPATCH(typed[tr.first].qc.elem,
@@ -1116,7 +1054,7 @@ int dq_quantile_summaries(dq_ctx* ctx, const dq_column* parts, const int32_t* pa
                           hipLaunchKernelGGL(q_compact_multi_kernel<E>, dim3(gxc, tr.second), dim3(kQBlock), 0, s,
                                              (const QPart*)(dtyped + tr.first), (const uint64_t*)dtree,
                                              (const uint32_t*)dtarget, dcursor, dcand))
-        QS_HIP(ctx, hipGetLastError());
+        DQ_CTX_HIP(ctx, hipGetLastError());
     }
 
     // ---- 5. order statistics: radix select per rank; a sort for requests with very many ranks ------------
@@ -1125,10 +1063,10 @@ int dq_quantile_summaries(dq_ctx* ctx, const dq_column* parts, const int32_t* pa
         QSelect* dsel;
         QM_ALLOC(dsel, QSelect, (int64_t)sel.size());
         QM_ALLOC(dout, double, (int64_t)sel.size());
-        QS_HIP(ctx, hipMemcpyAsync(dsel, sel.data(), sizeof(QSelect) * sel.size(), hipMemcpyHostToDevice, s));
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(dsel, sel.data(), sizeof(QSelect) * sel.size(), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(q_select_kernel, dim3((unsigned int)sel.size()), dim3(256), 0, s, (const uint64_t*)dcand,
                            (const QSelect*)dsel, dout);
-        QS_HIP(ctx, hipGetLastError());
+        DQ_CTX_HIP(ctx, hipGetLastError());
     }
     std::vector<std::vector<double>> sorted_vals(sorts.size());
     for (size_t j = 0; j < sorts.size(); ++j) {
@@ -1137,26 +1075,26 @@ int dq_quantile_summaries(dq_ctx* ctx, const dq_column* parts, const int32_t* pa
         uint64_t* dsrt;
         QM_ALLOC(dsrt, uint64_t, q.ncand);
         size_t tb = 0;
-        QS_HIP(ctx, rocprim::radix_sort_keys(nullptr, tb, dcand + q.base, dsrt, (size_t)q.ncand, 0, 64, s));
-        void* dt = scr.get(tb);
-        if (!dt) return dq::ctx_fail(ctx, DQ_ERR_DEVICE, "dq_quantile_summaries: out of device memory");
-        QS_HIP(ctx, rocprim::radix_sort_keys(dt, tb, dcand + q.base, dsrt, (size_t)q.ncand, 0, 64, s));
+        DQ_CTX_HIP(ctx, rocprim::radix_sort_keys(nullptr, tb, dcand + q.base, dsrt, (size_t)q.ncand, 0, 64, s));
+        void* dt;
+        QM_ALLOC(dt, uint8_t, tb);
+        DQ_CTX_HIP(ctx, rocprim::radix_sort_keys(dt, tb, dcand + q.base, dsrt, (size_t)q.ncand, 0, 64, s));
         const int ng = (int)q.idx.size();
         int64_t* didx;
         double* dv;
         QM_ALLOC(didx, int64_t, ng);
         QM_ALLOC(dv, double, ng);
-        QS_HIP(ctx, hipMemcpyAsync(didx, q.idx.data(), sizeof(int64_t) * ng, hipMemcpyHostToDevice, s));
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(didx, q.idx.data(), sizeof(int64_t) * ng, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(q_gather_kernel, dim3((ng + 255) / 256), dim3(256), 0, s, (const uint64_t*)dsrt,
                            (const int64_t*)didx, ng, dv);
-        QS_HIP(ctx, hipGetLastError());
+        DQ_CTX_HIP(ctx, hipGetLastError());
         sorted_vals[j].resize(ng);
-        QS_HIP(ctx, hipMemcpyAsync(sorted_vals[j].data(), dv, sizeof(double) * ng, hipMemcpyDeviceToHost, s));
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(sorted_vals[j].data(), dv, sizeof(double) * ng, hipMemcpyDeviceToHost, s));
     }
     std::vector<double> got(sel.size());
     if (!sel.empty())
-        QS_HIP(ctx, hipMemcpyAsync(got.data(), dout, sizeof(double) * got.size(), hipMemcpyDeviceToHost, s));
-    QS_HIP(ctx, hipStreamSynchronize(s));
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(got.data(), dout, sizeof(double) * got.size(), hipMemcpyDeviceToHost, s));
+    DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
     for (size_t j = 0; j < sel.size(); ++j) values_out[sel[j].out] = got[j];
     for (size_t j = 0; j < sorts.size(); ++j)
         for (size_t i = 0; i < sorts[j].out.size(); ++i) values_out[sorts[j].out[i]] = sorted_vals[j][i];

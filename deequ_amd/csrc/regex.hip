@@ -9,11 +9,11 @@
 // NOT-NULL = every row: the expression is never NULL). Numbers are matched against their Spark
 // string cast (integral: decimal digits, boolean: "true"/"false").
 //
-// Program image (little-endian int32): header {magic, ninstr, nclasses, nranges, ngroups, nloops,
-// anchored, 0}, ninstr x {op, a, b}, nclasses x {first range, count}, nranges x {lo, hi}.
+// The program image is laid out as rx_engine.h describes (rx_program).
 #include <hip/hip_runtime.h>
 
 #include "dq_common.h"
+#include "dq_device.h"
 #include "dq_internal.h"
 #include "java_dtoa.h"
 #include "rx_engine.h"
@@ -27,17 +27,10 @@ __global__ void __launch_bounds__(256)
 regex_match_kernel(PredColumn col, const int32_t* __restrict__ image, int64_t nrows, int64_t padded_words,
                    uint64_t* __restrict__ out_t, uint64_t* __restrict__ out_nn, int32_t* __restrict__ status) {
     const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    RxProg p;
-    p.ninstr = image[1];
-    p.anchored = image[6];
-    p.ins = image + 8;
-    p.classes = p.ins + 3 * p.ninstr;
-    p.ranges = p.classes + 2 * image[2];
+    const RxProg p = rx_program(image);
     bool t = false;
     if (row < nrows) {
-        bool valid = true;
-        if (col.validity) valid = (col.validity[row >> 6] >> (row & 63)) & 1ull;
-        if (valid) {
+        if (row_valid(col.validity, row)) {
             uint8_t buf[32];
             const uint8_t* s;
             int n;
@@ -90,22 +83,10 @@ regex_match_kernel(PredColumn col, const int32_t* __restrict__ image, int64_t nr
                 }
             }
             uint64_t stk[kRxStack];
-            // Matcher.find(): the first start position (code point boundaries) with a match
-            for (int start = 0; start <= n;) {
-                const int end = rx_match_at(p, s, n, start, stk);
-                if (end == -2) {
-                    atomicOr(status, 1);
-                    break;
-                }
-                if (end >= 0) {
-                    t = end > start;  // regexp_extract(..., 0) != ""
-                    break;
-                }
-                if (p.anchored || start == n) break;
-                int len;
-                decode(s, n, start, len);
-                start += len;
-            }
+            int start;
+            const int end = rx_find(p, s, n, stk, start);
+            if (end == -2) atomicOr(status, 1);
+            t = end > start;  // regexp_extract(..., 0) != "": the first match is non-empty
         }
     }
     const uint64_t bt = __ballot(t);

@@ -5,6 +5,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <string.h>
 
 #include "dq_common.h"
 #include "dq_internal.h"
@@ -415,6 +416,45 @@ __device__ inline int rx_match_at(const RxProg& p, const uint8_t* s, int n, int 
         }
     }
     return -2;
+}
+
+// The program of an image (little-endian int32): header {magic, ninstr, nclasses, nranges, ngroups, nloops, anchored,
+// 0}, ninstr x {op, a, b}, nclasses x {first range, count}, nranges x {lo, hi}.
+__device__ __forceinline__ RxProg rx_program(const int32_t* image) {
+    RxProg p;
+    p.ninstr = image[1];
+    p.anchored = image[6];
+    p.ins = image + 8;
+    p.classes = p.ins + 3 * p.ninstr;
+    p.ranges = p.classes + 2 * image[2];
+    return p;
+}
+
+// Host check of an image of `len` bytes before it is uploaded: the header's counts add up to exactly its length, so
+// the kernels read nothing past it.
+static inline bool rx_image_ok(const void* image, int64_t len) {
+    if ((len & 3) || len < 32) return false;
+    int32_t h[4];
+    memcpy(h, image, sizeof(h));
+    return h[1] > 0 && h[2] >= 0 && h[3] >= 0 &&
+           len == 4 * (8 + 3 * (int64_t)h[1] + 2 * (int64_t)h[2] + 2 * (int64_t)h[3]);
+}
+
+// Matcher.find(): the first start position (code point boundaries) with a match. Returns that match's end with its
+// start in `start` (an empty match has end == start), -1 = no match, -2 = resource limit.
+// `inline` like rx_match_at, not __forceinline__: the compiler inlines both into the kernels either way, but forcing
+// this one moves rx_match_at's inlining ahead of it and the kernels then keep rx_match_at's loop marks in VGPRs
+// (regex_match_kernel: 84 instead of 48, 5 waves per SIMD instead of 7).
+__device__ inline int rx_find(const RxProg& p, const uint8_t* s, int n, uint64_t* stk, int& start, int xf = 0) {
+    for (start = 0; start <= n;) {
+        const int end = rx_match_at(p, s, n, start, stk, xf);
+        if (end != -1) return end;
+        if (p.anchored || start == n) break;
+        int len;
+        decode(s, n, start, len);
+        start += len;
+    }
+    return -1;
 }
 
 // Spark's cast of an integral value to its decimal string.

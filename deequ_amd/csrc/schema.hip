@@ -21,6 +21,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "dq_common.h"
+#include "dq_device.h"
 #include "dq_internal.h"
 #include "dq_schema_parse.h"
 #include "rx_engine.h"
@@ -28,7 +29,6 @@
 namespace dq {
 
 constexpr int kSchemaBlock = 256;
-constexpr int kSchemaStageWords = 512;  // per wave: 2 KB of a column's bytes for 64 rows
 
 struct SchemaDef {
     const uint8_t* bytes;
@@ -47,18 +47,11 @@ struct SchemaCounters {
     int32_t rx_status;           // a regex ran out of its backtracking budget
 };
 
-// UTF-8 characters (non-continuation bytes), UTF8String.numChars for valid UTF-8 (as strings.hip counts MinLength).
-__device__ __forceinline__ int schema_utf8_chars(const uint8_t* s, int n) {
-    int c = 0;
-    for (int i = 0; i < n; ++i) c += (s[i] & 0xC0) != 0x80;
-    return c;
-}
-
 template <bool RX>
 __global__ void __launch_bounds__(kSchemaBlock) __attribute__((amdgpu_waves_per_eu(7, 8)))
 schema_verdict_kernel(const SchemaDef* __restrict__ defs, int ndefs, int64_t nrows, uint64_t* __restrict__ true_bits,
                       uint64_t* __restrict__ false_bits, uint64_t* __restrict__ amb_bits, SchemaCounters* counters) {
-    __shared__ uint32_t stage[kSchemaBlock / 64][kSchemaStageWords];
+    __shared__ uint32_t stage[kSchemaBlock / 64][kStageWords];
     __shared__ unsigned long long wcnt[kSchemaBlock / 64][4];
     const int64_t stride = (int64_t)gridDim.x * kSchemaBlock;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -72,26 +65,14 @@ schema_verdict_kernel(const SchemaDef* __restrict__ defs, int ndefs, int64_t nro
         bool f = false, u = false, amb = false;
         for (int d = 0; d < ndefs; ++d) {
             const SchemaDef D = defs[d];
-            const bool rvalid = rin && (D.validity == nullptr || ((D.validity[r >> 6] >> (r & 63)) & 1ull));
+            const bool rvalid = rin && row_valid(D.validity, r);
             int32_t ro = 0, rlen = 0;
             if (rin) {
                 ro = D.offsets[r];
                 rlen = D.offsets[r + 1] - ro;
             }
-            // the wave's byte range [b0, b1) into LDS when it fits (dword loads from the 4-byte aligned a0; the
-            // bytes buffer is 4-byte aligned and padded, dq.h)
-            const uint8_t* sbase = nullptr;
-            const int64_t b0 = D.offsets[w0], b1 = D.offsets[wl];
-            const int64_t a0 = b0 & ~(int64_t)3;
-            const int64_t nwords = (b1 - a0 + 3) >> 2;
-            if (nwords <= kSchemaStageWords) {
-                const uint32_t* src = reinterpret_cast<const uint32_t*>(D.bytes + a0);
-                for (int64_t i = lane; i < nwords; i += 64) stage[wave][i] = src[i];
-                sbase = reinterpret_cast<const uint8_t*>(&stage[wave][0]);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            int64_t a0;
+            const uint8_t* sbase = stage_wave_bytes(stage[wave], D.bytes, D.offsets, w0, wl, lane, a0);
             const uint8_t* s = sbase ? sbase + (ro - a0) : D.bytes + ro;
             if (!D.nullable && rin && !rvalid) f = true;
             bool ok = false, a = false;
@@ -101,37 +82,17 @@ schema_verdict_kernel(const SchemaDef* __restrict__ defs, int ndefs, int64_t nro
                 case DQ_SCHEMA_STRING:
                     if (rvalid) {
                         if (D.has_min || D.has_max) {
-                            const int len = schema_utf8_chars(s, rlen);
+                            const int len = utf8_chars(s, rlen);
                             if (D.has_min && len < D.minv) f = true;
                             if (D.has_max && len > D.maxv) f = true;
                         }
                         if (RX && D.prog_len > 0 && !f) {  // only lanes not already FALSE run the matcher
-                            using namespace rx;
-                            const int32_t* image = static_cast<const int32_t*>(D.prog);
-                            RxProg p;
-                            p.ninstr = image[1];
-                            p.anchored = image[6];
-                            p.ins = image + 8;
-                            p.classes = p.ins + 3 * p.ninstr;
-                            p.ranges = p.classes + 2 * image[2];
-                            uint64_t stk[kRxStack];
-                            bool t = false;
-                            for (int start = 0; start <= rlen;) {  // Matcher.find(): first match, must be non-empty
-                                const int end = rx_match_at(p, s, rlen, start, stk);
-                                if (end == -2) {
-                                    atomicOr(&counters->rx_status, 1);
-                                    break;
-                                }
-                                if (end >= 0) {
-                                    t = end > start;
-                                    break;
-                                }
-                                if (p.anchored || start == rlen) break;
-                                int len;
-                                decode(s, rlen, start, len);
-                                start += len;
-                            }
-                            if (!t) f = true;
+                            const rx::RxProg p = rx::rx_program(static_cast<const int32_t*>(D.prog));
+                            uint64_t stk[rx::kRxStack];
+                            int start;
+                            const int end = rx::rx_find(p, s, rlen, stk, start);
+                            if (end == -2) atomicOr(&counters->rx_status, 1);
+                            if (end <= start) f = true;  // the first match must be non-empty
                         }
                     }
                     break;
@@ -229,7 +190,7 @@ gather_fixed_kernel(const T* __restrict__ in, const uint64_t* __restrict__ in_va
     if (k < nsel) {
         const int64_t r = idx[k];
         out[k] = in[r];
-        v = in_valid == nullptr || ((in_valid[r >> 6] >> (r & 63)) & 1ull);
+        v = row_valid(in_valid, r);
     }
     const unsigned long long b = __ballot(v);
     if ((threadIdx.x & 63) == 0 && out_valid && (k & ~(int64_t)63) < nsel) out_valid[k >> 6] = b;
@@ -245,7 +206,7 @@ gather_lengths_kernel(const int32_t* __restrict__ offsets, const uint64_t* __res
     if (k < nsel) {
         const int64_t r = idx[k];
         lens[k] = offsets[r + 1] - offsets[r];
-        v = in_valid == nullptr || ((in_valid[r >> 6] >> (r & 63)) & 1ull);
+        v = row_valid(in_valid, r);
     } else if (k == nsel) {
         lens[k] = 0;
     }
@@ -286,30 +247,9 @@ gather_bytes_kernel(const uint8_t* __restrict__ in, const int32_t* __restrict__ 
 }  // namespace dq
 
 namespace {
-struct SBuffers {
-    dq_ctx* ctx;
-    std::vector<std::pair<void*, size_t>> ptrs;
-    explicit SBuffers(dq_ctx* c) : ctx(c) {}
-    ~SBuffers() {
-        for (const auto& p : ptrs) dq::scratch_release(ctx, p.first, p.second);
-    }
-    hipError_t alloc(void** p, size_t bytes) {
-        bytes = std::max<size_t>(bytes, 16);
-        *p = dq::scratch_alloc(ctx, bytes);
-        if (!*p) return hipErrorOutOfMemory;
-        ptrs.push_back({*p, bytes});
-        return hipSuccess;
-    }
-};
 
 int blocks_of(int64_t n) { return (int)std::max<int64_t>(1, (n + 255) / 256); }
 }  // namespace
-
-#define SC_HIP(ctx, expr)                                                                         \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return dq::ctx_fail((ctx), DQ_ERR_DEVICE, hipGetErrorString(e_));   \
-    } while (0)
 
 extern "C" {
 
@@ -363,9 +303,7 @@ int dq_schema_validate(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t
         switch (sc.kind) {
             case DQ_SCHEMA_STRING:
                 if (sc.program_len > 0) {
-                    const int32_t* im = (const int32_t*)sc.program;
-                    if ((sc.program_len & 3) || sc.program_len < 32 || im[1] <= 0 || im[2] < 0 || im[3] < 0 ||
-                        (int64_t)sc.program_len != 4 * (8 + 3 * (int64_t)im[1] + 2 * (int64_t)im[2] + 2 * (int64_t)im[3]))
+                    if (!dq::rx::rx_image_ok(sc.program, sc.program_len))
                         return dq::ctx_fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_schema_validate: malformed regex program");
                     any_rx = true;
                 }
@@ -397,36 +335,36 @@ int dq_schema_validate(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t
     if (nrows == 0 || ndefs == 0) {
         // no definition: every row is TRUE (the fold starts from `true`)
         if (ndefs == 0 && nrows > 0) {
-            SC_HIP(ctx, hipSetDevice(dq::ctx_device(ctx)));
+            DQ_CTX_HIP(ctx, hipSetDevice(dq::ctx_device(ctx)));
             hipStream_t s0 = dq::ctx_stream(ctx);
             const size_t bb = (size_t)(nrows + 63) / 64 * 8;
-            if (true_bits) SC_HIP(ctx, hipMemsetAsync(true_bits, 0xFF, bb, s0));
-            if (false_bits) SC_HIP(ctx, hipMemsetAsync(false_bits, 0, bb, s0));
-            if (ambiguous_bits) SC_HIP(ctx, hipMemsetAsync(ambiguous_bits, 0, bb, s0));
-            SC_HIP(ctx, hipStreamSynchronize(s0));
+            if (true_bits) DQ_CTX_HIP(ctx, hipMemsetAsync(true_bits, 0xFF, bb, s0));
+            if (false_bits) DQ_CTX_HIP(ctx, hipMemsetAsync(false_bits, 0, bb, s0));
+            if (ambiguous_bits) DQ_CTX_HIP(ctx, hipMemsetAsync(ambiguous_bits, 0, bb, s0));
+            DQ_CTX_HIP(ctx, hipStreamSynchronize(s0));
             result->num_valid = nrows;
         }
         return DQ_OK;
     }
-    SC_HIP(ctx, hipSetDevice(dq::ctx_device(ctx)));
+    DQ_CTX_HIP(ctx, hipSetDevice(dq::ctx_device(ctx)));
     hipStream_t s = dq::ctx_stream(ctx);
-    SBuffers buf(ctx);
+    dq::ScratchBuffers buf(ctx);
     uint8_t* dprogs = nullptr;
     if (!progs.empty()) {
-        SC_HIP(ctx, buf.alloc((void**)&dprogs, progs.size()));
-        SC_HIP(ctx, hipMemcpyAsync(dprogs, progs.data(), progs.size(), hipMemcpyHostToDevice, s));
+        DQ_CTX_HIP(ctx, buf.alloc((void**)&dprogs, progs.size()));
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(dprogs, progs.data(), progs.size(), hipMemcpyHostToDevice, s));
         for (int d = 0; d < ndefs; ++d)
             if (hd[d].prog_len > 0) hd[d].prog = dprogs + prog_at[d];
     }
     dq::SchemaDef* ddefs = nullptr;
-    SC_HIP(ctx, buf.alloc((void**)&ddefs, sizeof(dq::SchemaDef) * (size_t)ndefs));
-    SC_HIP(ctx, hipMemcpyAsync(ddefs, hd.data(), sizeof(dq::SchemaDef) * (size_t)ndefs, hipMemcpyHostToDevice, s));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&ddefs, sizeof(dq::SchemaDef) * (size_t)ndefs));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(ddefs, hd.data(), sizeof(dq::SchemaDef) * (size_t)ndefs, hipMemcpyHostToDevice, s));
     dq::SchemaCounters hc;
     memset(&hc, 0, sizeof(hc));
     hc.first_ambiguous = INT_MAX;
     dq::SchemaCounters* dc = nullptr;
-    SC_HIP(ctx, buf.alloc((void**)&dc, sizeof(hc)));
-    SC_HIP(ctx, hipMemcpyAsync(dc, &hc, sizeof(hc), hipMemcpyHostToDevice, s));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&dc, sizeof(hc)));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(dc, &hc, sizeof(hc), hipMemcpyHostToDevice, s));
     // persistent workgroups, exactly as many as are resident at once: the rows of a tile cost very different amounts
     // (a regex against a NULL cell), so a partial second round of workgroups would leave CUs idle at the end
     const int64_t blocks = (nrows + dq::kSchemaBlock - 1) / dq::kSchemaBlock;
@@ -437,10 +375,10 @@ int dq_schema_validate(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(blocks, (int64_t)dq::ctx_cus(ctx) * per_cu));
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(dq::kSchemaBlock), 0, s, ddefs, ndefs, nrows, (uint64_t*)true_bits,
                        (uint64_t*)false_bits, (uint64_t*)ambiguous_bits, dc);
-    SC_HIP(ctx, hipGetLastError());
+    DQ_CTX_HIP(ctx, hipGetLastError());
     ctx->schema_launches++;
-    SC_HIP(ctx, hipMemcpyAsync(&hc, dc, sizeof(hc), hipMemcpyDeviceToHost, s));
-    SC_HIP(ctx, hipStreamSynchronize(s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(&hc, dc, sizeof(hc), hipMemcpyDeviceToHost, s));
+    DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
     result->num_valid = (int64_t)hc.n[0];
     result->num_invalid = (int64_t)hc.n[1];
     result->num_unknown = (int64_t)hc.n[2];
@@ -482,39 +420,39 @@ int dq_gather_rows(dq_ctx* ctx, const dq_column* column, int64_t nrows, const ui
         (!is_string && (((uintptr_t)out_values | (uintptr_t)column->values) & (uintptr_t)(esize - 1))))
         return dq::ctx_fail(ctx, DQ_ERR_ALIGNMENT, "dq_gather_rows: misaligned buffer");
     if (out_bytes) *out_bytes = 0;
-    SC_HIP(ctx, hipSetDevice(dq::ctx_device(ctx)));
+    DQ_CTX_HIP(ctx, hipSetDevice(dq::ctx_device(ctx)));
     hipStream_t s = dq::ctx_stream(ctx);
-    SBuffers buf(ctx);
+    dq::ScratchBuffers buf(ctx);
     const int64_t nwords = (nrows + 63) / 64;
     uint32_t *pc = nullptr, *wbase = nullptr;
-    SC_HIP(ctx, buf.alloc((void**)&pc, sizeof(uint32_t) * (size_t)(nwords + 1)));
-    SC_HIP(ctx, buf.alloc((void**)&wbase, sizeof(uint32_t) * (size_t)(nwords + 1)));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&pc, sizeof(uint32_t) * (size_t)(nwords + 1)));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&wbase, sizeof(uint32_t) * (size_t)(nwords + 1)));
     hipLaunchKernelGGL(dq::select_popc_kernel, dim3(blocks_of(nwords + 1)), dim3(256), 0, s, (const uint64_t*)select_bits,
                        nrows, nwords, pc);
-    SC_HIP(ctx, hipGetLastError());
+    DQ_CTX_HIP(ctx, hipGetLastError());
     size_t tb = 0;
-    SC_HIP(ctx, rocprim::exclusive_scan(nullptr, tb, pc, wbase, 0u, (size_t)(nwords + 1), rocprim::plus<uint32_t>(), s));
+    DQ_CTX_HIP(ctx, rocprim::exclusive_scan(nullptr, tb, pc, wbase, 0u, (size_t)(nwords + 1), rocprim::plus<uint32_t>(), s));
     void* tmp = nullptr;
-    SC_HIP(ctx, buf.alloc(&tmp, tb));
-    SC_HIP(ctx, rocprim::exclusive_scan(tmp, tb, pc, wbase, 0u, (size_t)(nwords + 1), rocprim::plus<uint32_t>(), s));
+    DQ_CTX_HIP(ctx, buf.alloc(&tmp, tb));
+    DQ_CTX_HIP(ctx, rocprim::exclusive_scan(tmp, tb, pc, wbase, 0u, (size_t)(nwords + 1), rocprim::plus<uint32_t>(), s));
     uint32_t total = 0;
-    SC_HIP(ctx, hipMemcpyAsync(&total, wbase + nwords, sizeof(total), hipMemcpyDeviceToHost, s));
-    SC_HIP(ctx, hipStreamSynchronize(s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(&total, wbase + nwords, sizeof(total), hipMemcpyDeviceToHost, s));
+    DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
     if ((int64_t)total != nselected)  // the output buffers were sized for nselected rows
         return dq::ctx_fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_gather_rows: nselected differs from the bitmap's set bits");
     if (nselected == 0) {
         if (is_string) {
-            SC_HIP(ctx, hipMemsetAsync(out_offsets, 0, sizeof(int32_t), s));
-            if (out_values) SC_HIP(ctx, hipMemsetAsync(out_values, 0, 16, s));
-            SC_HIP(ctx, hipStreamSynchronize(s));
+            DQ_CTX_HIP(ctx, hipMemsetAsync(out_offsets, 0, sizeof(int32_t), s));
+            if (out_values) DQ_CTX_HIP(ctx, hipMemsetAsync(out_values, 0, 16, s));
+            DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
         }
         return DQ_OK;
     }
     int32_t* idx = nullptr;
-    SC_HIP(ctx, buf.alloc((void**)&idx, sizeof(int32_t) * (size_t)nselected));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&idx, sizeof(int32_t) * (size_t)nselected));
     hipLaunchKernelGGL(dq::select_index_kernel, dim3(blocks_of(nrows)), dim3(256), 0, s, (const uint64_t*)select_bits, nrows,
                        wbase, idx);
-    SC_HIP(ctx, hipGetLastError());
+    DQ_CTX_HIP(ctx, hipGetLastError());
     const uint64_t* iv = (const uint64_t*)column->validity;
     uint64_t* ov = (uint64_t*)out_validity;
     if (!is_string) {
@@ -525,34 +463,34 @@ int dq_gather_rows(dq_ctx* ctx, const dq_column* column, int64_t nrows, const ui
             case 4: hipLaunchKernelGGL(dq::gather_fixed_kernel<uint32_t>, g, b, 0, s, (const uint32_t*)column->values, iv, idx, nselected, (uint32_t*)out_values, ov); break;
             default: hipLaunchKernelGGL(dq::gather_fixed_kernel<uint64_t>, g, b, 0, s, (const uint64_t*)column->values, iv, idx, nselected, (uint64_t*)out_values, ov); break;
         }
-        SC_HIP(ctx, hipGetLastError());
-        SC_HIP(ctx, hipStreamSynchronize(s));
+        DQ_CTX_HIP(ctx, hipGetLastError());
+        DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
         return DQ_OK;
     }
     if (!out_values) {  // sizing call: offsets, validity, total bytes
         int32_t* lens = nullptr;
-        SC_HIP(ctx, buf.alloc((void**)&lens, sizeof(int32_t) * (size_t)(nselected + 1)));
+        DQ_CTX_HIP(ctx, buf.alloc((void**)&lens, sizeof(int32_t) * (size_t)(nselected + 1)));
         hipLaunchKernelGGL(dq::gather_lengths_kernel, dim3(blocks_of(nselected + 1)), dim3(256), 0, s, column->offsets, iv, idx,
                            nselected, lens, ov);
-        SC_HIP(ctx, hipGetLastError());
+        DQ_CTX_HIP(ctx, hipGetLastError());
         size_t tb2 = 0;
-        SC_HIP(ctx, rocprim::exclusive_scan(nullptr, tb2, lens, out_offsets, 0, (size_t)(nselected + 1), rocprim::plus<int32_t>(), s));
+        DQ_CTX_HIP(ctx, rocprim::exclusive_scan(nullptr, tb2, lens, out_offsets, 0, (size_t)(nselected + 1), rocprim::plus<int32_t>(), s));
         void* tmp2 = nullptr;
-        SC_HIP(ctx, buf.alloc(&tmp2, tb2));
-        SC_HIP(ctx, rocprim::exclusive_scan(tmp2, tb2, lens, out_offsets, 0, (size_t)(nselected + 1), rocprim::plus<int32_t>(), s));
+        DQ_CTX_HIP(ctx, buf.alloc(&tmp2, tb2));
+        DQ_CTX_HIP(ctx, rocprim::exclusive_scan(tmp2, tb2, lens, out_offsets, 0, (size_t)(nselected + 1), rocprim::plus<int32_t>(), s));
         int32_t bytes = 0;
-        SC_HIP(ctx, hipMemcpyAsync(&bytes, out_offsets + nselected, sizeof(bytes), hipMemcpyDeviceToHost, s));
-        SC_HIP(ctx, hipStreamSynchronize(s));
+        DQ_CTX_HIP(ctx, hipMemcpyAsync(&bytes, out_offsets + nselected, sizeof(bytes), hipMemcpyDeviceToHost, s));
+        DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
         *out_bytes = bytes;
         return DQ_OK;
     }
     // copy call: out_offsets holds the sizing call's offsets; out_values has their total + 16 bytes
     hipLaunchKernelGGL(dq::gather_bytes_kernel, dim3((unsigned)((nselected + 255) / 256)), dim3(256), 0, s,
                        (const uint8_t*)column->values, column->offsets, idx, out_offsets, nselected, (uint8_t*)out_values);
-    SC_HIP(ctx, hipGetLastError());
+    DQ_CTX_HIP(ctx, hipGetLastError());
     int32_t bytes = 0;
-    SC_HIP(ctx, hipMemcpyAsync(&bytes, out_offsets + nselected, sizeof(bytes), hipMemcpyDeviceToHost, s));
-    SC_HIP(ctx, hipStreamSynchronize(s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(&bytes, out_offsets + nselected, sizeof(bytes), hipMemcpyDeviceToHost, s));
+    DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
     *out_bytes = bytes;
     return DQ_OK;
 }

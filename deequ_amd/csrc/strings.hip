@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "dq_common.h"
+#include "dq_device.h"
 #include "dq_internal.h"
 
 namespace dq {
@@ -379,7 +380,7 @@ __device__ __forceinline__ void string_groups(const uint8_t* __restrict__ data, 
             const int64_t row = base + 64 * j + lane;
             bool v = row < nrows;
             if (v) {
-                v = validity == nullptr || ((validity[row >> 6] >> (row & 63)) & 1ull);
+                v = row_valid(validity, row);
                 if (where_t) v = v && ((where_t[row >> 6] >> (row & 63)) & 1ull);
             }
             on[j] = v;
@@ -476,7 +477,7 @@ scan_strings_kernel(const StrSlot* __restrict__ slots, int nslots, int64_t nrows
             const int64_t row = b + lane;
             bool on = row < nrows;
             if (on) {
-                on = s.validity == nullptr || ((s.validity[row >> 6] >> (row & 63)) & 1ull);
+                on = row_valid(s.validity, row);
                 if (s.where_t) on = on && ((s.where_t[row >> 6] >> (row & 63)) & 1ull);
             }
             return on;

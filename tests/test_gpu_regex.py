@@ -224,3 +224,48 @@ def test_extended_regex_known_answers():
         t = Table([_column_from_pylist("s", "string", words)])
         st = states(t, [D.PatternMatch("s", pat)])[0]
         assert st.numMatches == sum(hits), (pat, st, hits)
+
+
+def test_malformed_program_images_are_rejected_before_any_launch():
+    """A regex image whose header does not add up to its byte length (ninstr raised, the last word dropped, one word
+    appended) is refused by the scan (PatternMatch's [COL, REGEX] and the VM's RLIKE: DQ_ERR_PREDICATE) and by
+    dq_schema_validate (DQ_ERR_INVALID_ARGUMENT): the kernels would read past the buffer."""
+    import ctypes
+    import deequ_amd.native as N
+    from deequ_amd import engine
+    from deequ_amd.expr import CompiledPredicate
+    from deequ_amd.regex import compile_regex
+
+    good = compile_regex(r"[a-c]+x").to_bytes()
+    words = np.frombuffer(good, dtype=np.int32).copy()
+    words[1] += 1
+    bad = {"ninstr raised": words.tobytes(), "last word dropped": good[:-4], "one word appended": good + b"\0" * 4}
+    t = Table([_column_from_pylist("s", "string", ["abx"])]).to_device(0)
+    ctx = engine.ctx()
+    op = N.DqOp()
+    op.kind, op.where, op.predicate = N.OP_COMPLIANCE, -1, 0
+    op.column[0] = op.column[1] = -1
+
+    def scan(opcode, image):
+        k = N.DqConst()
+        k.tag, k.str_len, k.str_offset = N.V_STRING, len(image), 0
+        pred = CompiledPredicate("malformed image", [N.P_COL, 0, opcode, 0], [k], image, ["s"])
+        return ctx.scan([t["s"].native()], 1, [op], [pred.to_native()])
+
+    def schema(image):
+        buf = ctypes.create_string_buffer(image, len(image))
+        sc = N.DqSchemaColumn()
+        sc.kind, sc.column, sc.nullable = N.SCHEMA_STRING, 0, 1
+        sc.program, sc.program_len = ctypes.addressof(buf), len(image)
+        return ctx.schema_validate([t["s"].native()], 1, [sc], 0, 0, 0, 0)[0]
+
+    for opcode in (N.P_REGEX, N.P_RLIKE):
+        assert scan(opcode, good)[0].present  # the intact image runs
+        for what, image in bad.items():
+            with pytest.raises(N.NativeError) as ei:
+                scan(opcode, image)
+            assert ei.value.status == -6 and "malformed" in str(ei.value), (opcode, what, ei.value)
+    assert schema(good) == N.DQ_OK
+    for what, image in bad.items():
+        assert schema(image) == -1, what
+        assert "malformed regex program" in ctx.last_error()

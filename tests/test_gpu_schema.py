@@ -156,6 +156,16 @@ def test_all_null_and_never_null_schema_columns():
     assert res.numValidRows > 0 and res.numUnknownRows == 0
 
 
+def test_pattern_whose_first_match_is_empty():
+    """`matches` needs the FIRST match of Matcher.find() to be non-empty: "ax" has the empty match of `x*` at 0 before
+    the "x" at 1, so it is invalid like ""; a NULL cell is valid. 130 rows: two full waves and a 2-row tail."""
+    cells = ["", "x", "ax", "xa", None]
+    rows = [["r%03d" % k, cells[k % 5]] for k in range(130)]
+    res, _ = check_against_model(["rowid", "s"], rows, [{"type": "string", "name": "s", "matches": "x*"}], True)
+    assert (res.numValidRows, res.numInvalidRows, res.numUnknownRows) == (78, 52, 0)
+    assert {r[1] for r in table_cells(res.invalidRows, True)} == {"", "ax"}
+
+
 # ---- 4. a randomized table -----------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def random_rows(n=20000, seed=77):
