@@ -85,6 +85,13 @@ bool scan_concurrency() {
     return e && e[0] == '1';
 }
 
+// DQ_SCAN_GRID=g (g >= 1): caps every scan group's grid at g workgroups, never raises it (read per call; tests/).
+int64_t scan_grid_cap() {
+    const char* e = getenv("DQ_SCAN_GRID");
+    const long v = e ? atol(e) : 0;
+    return v >= 1 ? (int64_t)v : INT64_MAX;
+}
+
 // Recognises the predicates pred_simple_kernel evaluates (see PredSimple): a symbolic run of the postfix program.
 bool compile_simple_predicate(const dq_predicate& pr, const dq_column* columns, int ncols, PredSimple& out) {
     memset(&out, 0, sizeof(out));
@@ -1080,6 +1087,7 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
         return (c.flags & all) == all && fast_pred;
     };
     std::map<int, int> group_of;
+    const int64_t grid_cap = scan_grid_cap();
     for (int s = 0; s < (int)slots.size(); ++s) {
         const SlotDesc& sd = slots[s];
         if (sd.kind == SK_WHERE) continue;
@@ -1105,7 +1113,8 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
             auto oc = ctx->occupancy.find(key);
             if (oc != ctx->occupancy.end()) occ = oc->second;
             else occ = ctx->occupancy[key] = std::max(1, scan_group_blocks_per_cu(kind, P, nc, f0, f1, heavy));
-            const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(std::max<int64_t>(ntiles, 1), (int64_t)ctx->cus * occ));
+            const int64_t planned = std::max<int64_t>(1, std::min<int64_t>(std::max<int64_t>(ntiles, 1), (int64_t)ctx->cus * occ));
+            const int64_t grid = std::min(planned, grid_cap);
             groups.push_back(Group{kind, P, nc, f0, f1, heavy, (int)grid, {}});
             it = group_of.emplace(key, (int)groups.size() - 1).first;
         }

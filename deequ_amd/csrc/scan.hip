@@ -35,6 +35,12 @@ namespace dq {
 #ifndef DQ_SCAN_AUX
 #define DQ_SCAN_AUX 2
 #endif
+// The validity words of the striped kernels keep the default policy: a tile's 256 bitmap bytes are two cache lines
+// that its 16 wave-level loads (4 waves x 4 loads, 32 lanes per word) read again and again, and nt sent every one
+// of them past the CU's vector cache. Default policy: both C2 launches 1.6-2.4 % shorter (profiles/r07/).
+#ifndef DQ_SCAN_BITS_AUX
+#define DQ_SCAN_BITS_AUX 0
+#endif
 
 __device__ __forceinline__ double as_f64(uint64_t u) { return __longlong_as_double((long long)u); }
 __device__ __forceinline__ uint64_t f64_bits(double d) { return (uint64_t)__double_as_longlong(d); }
@@ -301,7 +307,7 @@ __device__ __forceinline__ uint32_t bits_padded(const uint64_t* __restrict__ bm,
     for (int j = 0; j < L; ++j) {
         // row0 = tile + j * 256 * P + tid * P; its 64-bit word inside the tile and bit offset:
         const int rel = j * (kBlock * P) + tid * P;
-        const v2i_t w = __builtin_amdgcn_raw_buffer_load_b64(r, (rel >> 6) * 8, 0, DQ_SCAN_AUX);
+        const v2i_t w = __builtin_amdgcn_raw_buffer_load_b64(r, (rel >> 6) * 8, 0, DQ_SCAN_BITS_AUX);
         const uint64_t word = ((uint64_t)(uint32_t)w.y << 32) | (uint32_t)w.x;
         m |= (uint32_t)((word >> (rel & 63)) & pm) << (j * P);
     }
@@ -905,8 +911,12 @@ __device__ __forceinline__ void hll_update(uint32_t* regs, const uint64_t (&v)[8
 
 // ------------------------------------------------------------------------------------------------
 // Value slots: P rows per load, NC columns (2 = Correlation pair), F0/F1 = floating storage.
-// Workgroup g handles tiles g, g + G, g + 2G, ... (balanced for any grid size); the next tile's
-// loads are issued before the current tile is folded (register double buffer).
+// Workgroup g handles tiles g, g + G, g + 2G, ... (balanced for any grid size). The next tile's value
+// loads are issued before the current tile is folded, but the current tile's validity words are requested
+// after them and vector loads retire in order, so the wait in front of the fold drains that prefetch too
+// (s_waitcnt vmcnt(0)): a wave has one tile in flight and none while it folds; the overlap comes from the
+// 3 waves per SIMD. A true two-set pipeline (both sets issued ahead, counted waits, loop unrolled by two)
+// was built and measured no faster on either C2 launch (tried and dropped).
 // ------------------------------------------------------------------------------------------------
 template <int NC, bool F0, bool F1>
 struct BlockRed {
