@@ -25,6 +25,11 @@ from .profiles import (ColumnProfiler, ColumnProfilerRunner, ColumnProfilerRunBu
                        StandardColumnProfile, NumericColumnProfile, DataTypeInstances)
 from .state_provider import HdfsStateProvider, FileSystemStateProvider
 from .schema import (RowLevelSchema, RowLevelSchemaValidator, RowLevelSchemaValidationResult)
+from .suggestions import (ConstraintSuggestionRunner, ConstraintSuggestionRunBuilder, ConstraintSuggestionResult,
+                          ConstraintSuggestion, ConstraintSuggestions, ConstraintRule, Rules, CompleteIfCompleteRule,
+                          RetainCompletenessRule, RetainTypeRule, CategoricalRangeRule,
+                          FractionalCategoricalRangeRule, NonNegativeNumbersRule, UniqueIfApproximatelyUniqueRule,
+                          split_train_test)
 from . import distributed
 
 __all__ = [n for n in dir() if not n.startswith("_")]

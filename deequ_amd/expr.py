@@ -326,6 +326,8 @@ class CompiledPredicate:
         return p
 
 
+_IN_WHOLE = 15  # the longest IN list emitted as one P_IN: x and 15 constants fill the VM's 16-entry stack
+_IN_GROUP = 8   # longer lists: P_IN over groups of 8, joined by P_OR
 _CMP = {"=": N.P_EQ, "!=": N.P_NE, "<": N.P_LT, "<=": N.P_LE, ">": N.P_GT, ">=": N.P_GE, "<=>": N.P_EQ_NULLSAFE}
 _ARITH = {"+": N.P_ADD, "-": N.P_SUB, "*": N.P_MUL, "/": N.P_DIV, "%": N.P_MOD}
 
@@ -397,9 +399,23 @@ def compile_predicate(text, column_index, column_types=None):
             emit(n.children[0])
             code.extend([N.P_IS_NULL if k == "isnull" else N.P_IS_NOT_NULL, 0])
         elif k == "in":
-            for ch in n.children:
-                emit(ch)
-            code.extend([N.P_IN, len(n.children) - 1])
+            items = n.children[1:]
+            if len(items) <= _IN_WHOLE:
+                for ch in n.children:
+                    emit(ch)
+                code.extend([N.P_IN, len(items)])
+            else:
+                # the VM's value stack holds 16 entries (kPredStack, dq_internal.h), so a longer list (the range of
+                # a categorical column: up to the histogram threshold's 120 values) runs as
+                # `x IN (first 8) OR x IN (next 8) OR ...`: the same three-valued result, x evaluated once per group
+                for at in range(0, len(items), _IN_GROUP):
+                    group = items[at:at + _IN_GROUP]
+                    emit(n.children[0])
+                    for ch in group:
+                        emit(ch)
+                    code.extend([N.P_IN, len(group)])
+                    if at:
+                        code.extend([N.P_OR, 0])
         elif k == "coalesce":
             for ch in n.children:
                 emit(ch)

@@ -72,7 +72,7 @@ EXPORTED_SYMBOLS = (
     "dq_scan_streamed", "dq_scan_kernel_launches", "dq_freq_path_count", "dq_kll_sketch_columns",
     "dq_kll_merge_states", "dq_scratch_trim", "dq_frequencies_parts", "dq_set_priority",
     "dq_schema_validate", "dq_schema_launch_count", "dq_gather_rows", "dq_parse_int32", "dq_parse_decimal",
-    "dq_parse_timestamp",
+    "dq_parse_timestamp", "dq_split_rows", "dq_split_row_is_test",
 )
 
 
@@ -286,6 +286,9 @@ def load_library(path=None):
             "dq_parse_decimal": (c_int, [ctypes.c_char_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_void_p]),
             "dq_parse_timestamp": (c_int, [ctypes.c_char_p, ctypes.c_int32, ctypes.c_char_p, ctypes.c_int32,
                                            c_void_p]),
+            "dq_split_rows": (c_int, [c_void_p, c_int64, c_int64, ctypes.c_uint64, ctypes.c_double, c_void_p, c_void_p,
+                                      c_void_p, c_void_p]),
+            "dq_split_row_is_test": (c_int, [c_int64, ctypes.c_uint64, ctypes.c_double]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name)
@@ -322,6 +325,11 @@ def parse_timestamp(program, cell):
     out = ctypes.c_int64(0)
     rc = load_library().dq_parse_timestamp(program, len(program), cell, len(cell), ctypes.byref(out))
     return rc, (int(out.value) if rc == PARSE_VALUE else None)
+
+
+def split_row_is_test(global_row, seed, test_ratio):
+    """dq_split_row_is_test: 1 = the row is in the TEST set, 0 = TRAIN, < 0 = bad argument (host-side, C-ABI)."""
+    return int(load_library().dq_split_row_is_test(int(global_row), int(seed) & 0xFFFFFFFFFFFFFFFF, float(test_ratio)))
 
 
 def kll_merge_states(a, b):
@@ -577,6 +585,17 @@ class Context:
                                            ctypes.c_void_p(offsets_ptr) if offsets_ptr else None, ctypes.byref(nbytes)),
                    "dq_gather_rows")
         return int(nbytes.value)
+
+    def split_rows(self, nrows, row0, seed, test_ratio, train_ptr, test_ptr):
+        """dq_split_rows into two device bitmaps (either pointer may be None); returns (num_train, num_test)."""
+        self._after_torch_stream()
+        ntrain, ntest = ctypes.c_int64(0), ctypes.c_int64(0)
+        self.check(self.lib.dq_split_rows(self.handle, int(nrows), int(row0), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                          float(test_ratio), ctypes.c_void_p(train_ptr) if train_ptr else None,
+                                          ctypes.c_void_p(test_ptr) if test_ptr else None, ctypes.byref(ntrain),
+                                          ctypes.byref(ntest)),
+                   "dq_split_rows")
+        return int(ntrain.value), int(ntest.value)
 
     def _after_torch_stream(self):
         """The generators run on the context's stream; a buffer torch just allocated and filled (torch.zeros) on its

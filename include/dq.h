@@ -538,6 +538,21 @@ int dq_parse_int32(const uint8_t* s, int32_t n, int32_t* out);
 int dq_parse_decimal(const uint8_t* s, int32_t n, int32_t precision, int32_t scale, int64_t* out);
 int dq_parse_timestamp(const uint8_t* program, int32_t program_len, const uint8_t* s, int32_t n, int64_t* out);
 
+/* Train / test row split (ConstraintSuggestionRunner.useTrainTestSplitWithTestsetRatio). Row r of this call is global
+ * row g = row0 + r. h = XXH64 of the 8 little-endian bytes of g with seed `seed`: Spark's XXH64.hashLong(g, seed), the
+ * function the HLL scan computes with seed 42. Row r is in the TEST set iff
+ * (h >> 11) < (uint64_t)(test_ratio * 9007199254740992.0), otherwise in the TRAIN set: membership depends on
+ * (seed, g, test_ratio) alone, not on how a table is cut into calls. Both bitmaps are device buffers, 8-B aligned,
+ * LSB-first, (nrows + 63) / 64 words; EVERY word is written, and bits at and past nrows are 0. Either bitmap may be
+ * NULL (that side is not wanted); the counts are always returned. One kernel launch per call (none for nrows == 0).
+ * DQ_ERR_INVALID_ARGUMENT unless 0 < test_ratio < 1, nrows >= 0, row0 >= 0 and row0 + nrows fits an int64;
+ * DQ_ERR_ALIGNMENT for a misaligned bitmap; DQ_ERR_UNSUPPORTED on a multi-device context. */
+int dq_split_rows(dq_ctx* ctx, int64_t nrows, int64_t row0, uint64_t seed, double test_ratio, uint8_t* train_bits,
+                  uint8_t* test_bits, int64_t* num_train, int64_t* num_test);
+/* The same membership for one row, host only (no context, no device): 1 = test, 0 = train, < 0 = bad argument
+ * (global_row < 0 or a ratio outside ]0, 1[). The same code as the kernel. */
+int dq_split_row_is_test(int64_t global_row, uint64_t seed, double test_ratio);
+
 /* Multi-GPU grouping: the canonical 64-bit keys (see DQ_FREQ_KEYS_VALUES) of one
  * fixed-width column's non-NULL rows, bucketed by owner rank = (mix64(key) >> 32) % nparts, written
  * contiguously per rank into keys_dev (capacity nrows, device memory) for an RCCL all-to-all; the
