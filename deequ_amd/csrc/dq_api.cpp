@@ -1246,7 +1246,7 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
             DQ_HIP(ctx, hipMemcpyAsync(dst, h, n, hipMemcpyHostToDevice, ctx->stream));
             return DQ_OK;
         };
-        bool any_regex = false;
+        bool any_status = false;  // some predicate may set its status word: read the words back after the scan
         if (npred_pass || nstandalone) {
             DQ_HIP(ctx, hipMemsetAsync(rx_status, 0, sizeof(int32_t) * std::max(npreds, 1), ctx->stream));
             std::vector<PredColumn> pc(std::max(ncols, 1));
@@ -1287,17 +1287,24 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
                     launch_regex(pc[pr.code[1]], (const int32_t*)((const uint8_t*)pstr[p] + k.str_offset), nrows, pwords,
                                  pt[p], pn[p], rx_status + p, ctx->stream);
                     ctx->kernel_launches[DQ_KERNEL_REGEX]++;
-                    any_regex = true;
+                    any_status = true;
                 } else if (PredSimple ps; !pred_vm_forced() && compile_simple_predicate(pr, columns, ncols, ps)) {
                     launch_pred_simple(ps, (const PredColumn*)pcols, nrows, pwords, pt[p], pn[p], ctx->stream);
                     ctx->kernel_launches[DQ_KERNEL_PRED_SIMPLE]++;
                 } else {
-                    bool rx = false;
-                    for (int k = 0; k + 1 < pr.code_len; k += 2) rx |= pr.code[k] == DQ_P_RLIKE;
+                    // rx: the program holds RLIKE; str: it has a string operand, which a comparison, arithmetic or
+                    // CAST may have to convert to DOUBLE (a conversion the device cannot round exactly sets status)
+                    bool rx = false, str = false;
+                    for (int k = 0; k + 1 < pr.code_len; k += 2) {
+                        const int a = pr.code[k + 1];
+                        rx |= pr.code[k] == DQ_P_RLIKE;
+                        str |= pr.code[k] == DQ_P_COL && a >= 0 && a < ncols && columns[a].spark_type == DQ_TYPE_STRING;
+                        str |= pr.code[k] == DQ_P_CONST && a >= 0 && a < pr.n_consts && pr.consts[a].tag == DQ_V_STRING;
+                    }
                     launch_predicate((const PredProgram*)pprog[p], rx, rx_status + p, (const PredColumn*)pcols, nrows,
                                      pwords, pt[p], pn[p], ctx->stream);
                     ctx->kernel_launches[DQ_KERNEL_PRED_VM]++;
-                    any_regex |= rx;
+                    any_status |= rx || str;
                 }
                 DQ_HIP(ctx, hipGetLastError());
             }
@@ -1440,14 +1447,20 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
             launch_finalize_strings(dsops, (int)sopmap.size(), spartials, sgrid, gstride, nrows, dout, ctx->stream);
             DQ_HIP(ctx, hipGetLastError());
         }
-        if (any_regex) {
-            // a row that exhausted the backtracking budget fails the batch (never a silent count)
+        if (any_status) {
+            // a row that exhausted the backtracking budget, or whose string the device cannot convert to DOUBLE
+            // exactly, fails the batch (never a silent count)
             int32_t* hs = (int32_t*)hb.take(sizeof(int32_t) * std::max(npreds, 1), 16);
             DQ_HIP(ctx, hipMemcpyAsync(hs, rx_status, sizeof(int32_t) * std::max(npreds, 1), hipMemcpyDeviceToHost, ctx->stream));
             DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));
             for (int p = 0; p < npreds; ++p)
-                if (pred_pass[p] && hs[p])
+                if (pred_pass[p] && (hs[p] & 1))
                     return fail(ctx, DQ_ERR_UNSUPPORTED, "predicate %d: regex backtracking limit exceeded", p);
+            for (int p = 0; p < npreds; ++p)
+                if (pred_pass[p] && hs[p])
+                    return fail(ctx, DQ_ERR_UNSUPPORTED,
+                                "predicate %d: a string needs Double.parseDouble's arbitrary-precision path "
+                                "(hexadecimal literal, or > 19 significant digits on a rounding boundary)", p);
         }
         if (!(flags & DQ_SCAN_OUT_DEVICE)) {
             void* h = hb.take(sizeof(dq_state) * nops, 16);

@@ -19,7 +19,11 @@
 #include "ryu_tables.h"
 
 #ifndef DQ_HD
+#if defined(DQ_HOST_ONLY)  // host-only build (tests/number_text_host/): the same routines over the _h tables, no HIP
+#define DQ_HD inline
+#else
 #define DQ_HD __host__ __device__ __forceinline__
+#endif
 #endif
 
 namespace dq {

@@ -65,60 +65,19 @@ __device__ __forceinline__ Val vdouble(double x) {
 
 __device__ __forceinline__ bool is_ws(uint8_t c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r'; }
 
-__device__ const double kPow10[23] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
-                                      1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
+// Status bits of a predicate's status word (read back by dq_scan, which fails the batch on any of them).
+constexpr int32_t kPredStatusRegexBudget = 1;   // a regex ran out of its backtracking budget
+constexpr int32_t kPredStatusInexactDouble = 2; // a string -> double conversion the device cannot round exactly
 
-// Spark Cast(string -> double) = java.lang.Double.parseDouble, correctly rounded (dq_parse.h). The
-// rare literal it cannot round on the device (hexadecimal, or > 19 significant digits on a rounding
-// boundary) falls back to a plain decimal scale here: predicates have no per-row error channel.
-__device__ bool parse_double_approx(const uint8_t* s, int n, double& out) {
-    int i = 0;
-    while (i < n && s[i] <= ' ') ++i;
-    while (n > i && s[n - 1] <= ' ') --n;
-    if (i >= n) return false;
-    bool neg = false;
-    if (s[i] == '+' || s[i] == '-') {
-        neg = s[i] == '-';
-        ++i;
-    }
-    double v = 0.0;
-    int exp10 = 0, nd = 0;
-    bool seen_dot = false;
-    for (; i < n; ++i) {
-        const uint8_t c = s[i];
-        if (c >= '0' && c <= '9') {
-            ++nd;
-            v = v * 10.0 + (c - '0');
-            if (seen_dot) --exp10;
-        } else if (c == '.' && !seen_dot) {
-            seen_dot = true;
-        } else {
-            break;
-        }
-    }
-    if (nd == 0) return false;
-    if (i < n && (s[i] == 'e' || s[i] == 'E')) {
-        ++i;
-        bool eneg = false;
-        if (i < n && (s[i] == '+' || s[i] == '-')) {
-            eneg = s[i] == '-';
-            ++i;
-        }
-        int e = 0;
-        for (; i < n && s[i] >= '0' && s[i] <= '9'; ++i) e = e < 10000 ? e * 10 + (s[i] - '0') : e;
-        exp10 += eneg ? -e : e;
-    }
-    while (exp10 > 22) { v *= 1e22; exp10 -= 22; }
-    while (exp10 < -22) { v /= 1e22; exp10 += 22; }
-    v = exp10 >= 0 ? v * kPow10[exp10] : v / kPow10[-exp10];
-    out = neg ? -v : v;
-    return true;
-}
-
-__device__ bool parse_double(const uint8_t* s, int n, double& out) {
+// Spark Cast(string -> double) = java.lang.Double.parseDouble, correctly rounded (dq_parse.h). The rare
+// literal it cannot round on the device (a well-formed hexadecimal literal, or > 19 significant digits on a
+// rounding boundary) is never guessed: the row sets kPredStatusInexactDouble and the batch fails with
+// DQ_ERR_UNSUPPORTED, as dq_cast_column does for the same strings.
+__device__ bool parse_double(const uint8_t* s, int n, double& out, int32_t* status) {
     bool slow = false;
     if (java_parse_double(s, n, out, slow)) return true;
-    return slow ? parse_double_approx(s, n, out) : false;
+    if (slow) atomicOr(status, kPredStatusInexactDouble);
+    return false;
 }
 
 // Spark 2.2 Cast(string -> long) = UTF8String.toLong (dq_parse.h).
@@ -170,16 +129,16 @@ __device__ __forceinline__ const uint8_t* str_bytes(const Val& v, uint8_t (&buf)
     return buf;
 }
 
-__device__ bool parse_double_v(const Val& v, double& out) {
+__device__ bool parse_double_v(const Val& v, double& out, int32_t* status) {
     uint8_t buf[64];
     int n;
     const uint8_t* p = str_bytes(v, buf, n);
-    return parse_double(p, n, out);
+    return parse_double(p, n, out, status);
 }
 
 // Coerce a string operand against a numeric one the way Spark 2.x PromoteStrings does
 // (string -> double). Returns false when the string does not parse (comparison is NULL).
-__device__ bool compare(const Val& a, const Val& b, int& c) {
+__device__ bool compare(const Val& a, const Val& b, int& c, int32_t* status) {
     if (a.tag == DQ_V_STRING && b.tag == DQ_V_STRING) {
         c = cmp_str(a, b);
         return true;
@@ -187,12 +146,12 @@ __device__ bool compare(const Val& a, const Val& b, int& c) {
     if (a.tag == DQ_V_STRING || b.tag == DQ_V_STRING) {
         double x, y;
         if (a.tag == DQ_V_STRING) {
-            if (!parse_double_v(a, x)) return false;
+            if (!parse_double_v(a, x, status)) return false;
         } else {
             x = as_double(a);
         }
         if (b.tag == DQ_V_STRING) {
-            if (!parse_double_v(b, y)) return false;
+            if (!parse_double_v(b, y, status)) return false;
         } else {
             y = as_double(b);
         }
@@ -320,17 +279,17 @@ __device__ Val load_col(const PredColumn& c, int64_t row) {
     }
 }
 
-__device__ Val arith(int op, const Val& a, const Val& b) {
+__device__ Val arith(int op, const Val& a, const Val& b, int32_t* status) {
     if (a.null || b.null) return vnull();
     Val x = a, y = b;
     if (x.tag == DQ_V_STRING) {
         double d;
-        if (!parse_double_v(x, d)) return vnull();
+        if (!parse_double_v(x, d, status)) return vnull();
         x = vdouble(d);
     }
     if (y.tag == DQ_V_STRING) {
         double d;
-        if (!parse_double_v(y, d)) return vnull();
+        if (!parse_double_v(y, d, status)) return vnull();
         y = vdouble(d);
     }
     const bool integral = x.tag != DQ_V_DOUBLE && y.tag != DQ_V_DOUBLE;
@@ -428,7 +387,7 @@ predicate_kernel(const PredProgram* __restrict__ progp, const PredColumn* __rest
                     const Val b = st[--sp];
                     const Val a = st[--sp];
                     int c = 0;
-                    if (a.null || b.null || !compare(a, b, c)) {
+                    if (a.null || b.null || !compare(a, b, c, status)) {
                         st[sp++] = vnull();
                         break;
                     }
@@ -449,7 +408,7 @@ predicate_kernel(const PredProgram* __restrict__ progp, const PredColumn* __rest
                     const Val a = st[--sp];
                     int c = 1;
                     if (a.null || b.null) st[sp++] = vbool(a.null && b.null);
-                    else st[sp++] = vbool(compare(a, b, c) && c == 0);
+                    else st[sp++] = vbool(compare(a, b, c, status) && c == 0);
                     break;
                 }
                 case DQ_P_AND: {
@@ -490,7 +449,7 @@ predicate_kernel(const PredProgram* __restrict__ progp, const PredColumn* __rest
                             const Val& e = st[base + 1 + k];
                             int c = 1;
                             if (e.null) any_null = true;
-                            else if (compare(x, e, c) && c == 0) hit = true;
+                            else if (compare(x, e, c, status) && c == 0) hit = true;
                         }
                         r = hit ? vbool(true) : (any_null ? vnull() : vbool(false));
                     }
@@ -511,7 +470,7 @@ predicate_kernel(const PredProgram* __restrict__ progp, const PredColumn* __rest
                 case DQ_P_ADD: case DQ_P_SUB: case DQ_P_MUL: case DQ_P_DIV: case DQ_P_MOD: {
                     const Val b = st[--sp];
                     const Val a = st[--sp];
-                    st[sp++] = arith(op, a, b);
+                    st[sp++] = arith(op, a, b, status);
                     break;
                 }
                 case DQ_P_NEG: {
@@ -553,7 +512,7 @@ predicate_kernel(const PredProgram* __restrict__ progp, const PredColumn* __rest
                         uint64_t stk[rx::kRxStack];
                         int start;
                         const int end = rx::rx_find(rp, sv, n, stk, start, xf);
-                        if (end == -2) atomicOr(status, 1);
+                        if (end == -2) atomicOr(status, kPredStatusRegexBudget);
                         st[sp - 1] = vbool(end >= 0);
                     }
                     st_type[sp - 1] = 0;
@@ -620,7 +579,7 @@ predicate_kernel(const PredProgram* __restrict__ progp, const PredColumn* __rest
                     bool r = false;
                     if (!a.null) {
                         if (a.tag == DQ_V_DOUBLE) r = a.d != a.d;
-                        else if (a.tag == DQ_V_STRING) { double d; r = parse_double_v(a, d) && d != d; }
+                        else if (a.tag == DQ_V_STRING) { double d; r = parse_double_v(a, d, status) && d != d; }
                     }
                     st[sp - 1] = vbool(r);
                     st_type[sp - 1] = 0;
@@ -629,7 +588,7 @@ predicate_kernel(const PredProgram* __restrict__ progp, const PredColumn* __rest
                 case DQ_P_ABS: {
                     Val& a = st[sp - 1];
                     if (!a.null) {
-                        if (a.tag == DQ_V_STRING) { double d; a = parse_double_v(a, d) ? vdouble(fabs(d)) : vnull(); }
+                        if (a.tag == DQ_V_STRING) { double d; a = parse_double_v(a, d, status) ? vdouble(fabs(d)) : vnull(); }
                         else if (a.tag == DQ_V_DOUBLE) a.d = fabs(a.d);
                         else if (a.i < 0) a.i = (int64_t)(0ull - (uint64_t)a.i);  // Long.MinValue stays (Math.abs)
                     }
@@ -666,7 +625,7 @@ predicate_kernel(const PredProgram* __restrict__ progp, const PredColumn* __rest
                     if (a.null) break;
                     if (a.tag == DQ_V_STRING) {
                         double d;
-                        st[sp - 1] = parse_double(a.s, a.slen, d) ? vdouble(d) : vnull();
+                        st[sp - 1] = parse_double(a.s, a.slen, d, status) ? vdouble(d) : vnull();
                     } else {
                         st[sp - 1] = vdouble(as_double(a));
                     }
@@ -679,7 +638,14 @@ predicate_kernel(const PredProgram* __restrict__ progp, const PredColumn* __rest
                         int64_t x;
                         st[sp - 1] = parse_long(a.s, a.slen, x) ? vlong(x) : vnull();
                     } else if (a.tag == DQ_V_DOUBLE) {
-                        st[sp - 1] = a.d != a.d ? vlong(0) : vlong((int64_t)a.d);
+                        // Java's d.toLong: truncation, saturating at Long.MIN_VALUE / MAX_VALUE, NaN -> 0 (a plain
+                        // conversion of a value outside the range is undefined)
+                        int64_t x;
+                        if (a.d != a.d) x = 0;
+                        else if (a.d >= 9223372036854775808.0) x = INT64_MAX;
+                        else if (a.d <= -9223372036854775808.0) x = INT64_MIN;
+                        else x = (int64_t)a.d;
+                        st[sp - 1] = vlong(x);
                     } else {
                         st[sp - 1] = vlong(a.i);
                     }

@@ -101,6 +101,11 @@ typedef enum dq_pred_opcode {
     DQ_P_ADD = 30, DQ_P_SUB = 31, DQ_P_MUL = 32, DQ_P_DIV = 33, DQ_P_MOD = 34, DQ_P_NEG = 35,
     DQ_P_LIKE = 40,      /* arg: constant index of the pattern; 1 operand                      */
     DQ_P_LENGTH = 41,    /* UTF-8 character count                                             */
+    /* Spark 2.2 Cast: string -> DOUBLE is Double.parseDouble (NULL where it throws), string -> LONG is
+     * UTF8String.toLong, DOUBLE -> LONG is Java's d.toLong (saturating, NaN -> 0). A string whose double needs
+     * parseDouble's arbitrary-precision path (a hexadecimal literal, or more than 19 significant digits on a rounding
+     * boundary) fails the dq_scan call with DQ_ERR_UNSUPPORTED, as dq_cast_column does; so does such a string in a
+     * comparison with a number, in arithmetic, abs or isnan (Spark's implicit string -> double cast). */
     DQ_P_CAST_DOUBLE = 42, DQ_P_CAST_LONG = 43, DQ_P_CAST_STRING_NUM = 44,
     /* PatternMatch (A/PatternMatch.scala:46-48): arg = index of a STRING constant holding a compiled
      * java.util.regex program (deequ_amd/regex.py image, 4-byte aligned in the pool); 1 operand.

@@ -831,11 +831,10 @@ def _cmp_vals(a, b):
     if isinstance(a, str) and isinstance(b, str):
         ab, bb = a.encode(), b.encode()
         return (ab > bb) - (ab < bb)
-    if isinstance(a, str) or isinstance(b, str):
-        try:
-            a = float(a) if isinstance(a, str) else float(a)
-            b = float(b) if isinstance(b, str) else float(b)
-        except ValueError:
+    if isinstance(a, str) or isinstance(b, str):  # the string side through Double.parseDouble, never Python's float()
+        a = java_parse_double(a) if isinstance(a, str) else float(a)
+        b = java_parse_double(b) if isinstance(b, str) else float(b)
+        if a is None or b is None:
             return None
     if isinstance(a, bool):
         a = int(a)
@@ -923,8 +922,10 @@ def _eval(node, row):
         a, b = _eval(node.children[0], row), _eval(node.children[1], row)
         if a is None or b is None:
             return None
-        a = float(a) if isinstance(a, str) else a
-        b = float(b) if isinstance(b, str) else b
+        a = java_parse_double(a) if isinstance(a, str) else a
+        b = java_parse_double(b) if isinstance(b, str) else b
+        if a is None or b is None:
+            return None
         op = node.value
         if op == "/":
             return None if b == 0 else float(a) / float(b)
@@ -945,22 +946,25 @@ def _eval(node, row):
     if k == "length":
         a = _eval(node.children[0], row)
         return None if a is None else len(a)
-    if k == "cast_double":
+    if k == "cast_double":  # Cast(string -> double) is Double.parseDouble (NULL where it throws), not Python's float()
         a = _eval(node.children[0], row)
         if a is None:
             return None
-        try:
-            return float(a)
-        except ValueError:
-            return None
+        return java_parse_double(a) if isinstance(a, str) else float(a)
     if k == "cast_long":
+        # Cast(string -> long) is UTF8String.toLong (no exponent, no trimming: NULL); Cast(double -> long) is Java's
+        # d.toLong: truncation towards zero, saturating at Long.MIN_VALUE / MAX_VALUE, NaN -> 0
         a = _eval(node.children[0], row)
         if a is None:
             return None
-        try:
-            return int(float(a)) if isinstance(a, str) else int(a)
-        except ValueError:
-            return None
+        if isinstance(a, str):
+            return spark_string_to_long(a)
+        if isinstance(a, float):
+            if a != a:
+                return 0
+            return max(-(1 << 63), min((1 << 63) - 1, int(a))) if math.isfinite(a) else \
+                ((1 << 63) - 1 if a > 0 else -(1 << 63))
+        return int(a)
     if k == "case":
         parts, other = node.value
         for cond, val in parts:
@@ -1000,17 +1004,12 @@ def _eval(node, row):
         a = _eval(node.children[0], row)
         if a is None:
             return False
-        try:
-            return math.isnan(float(a))
-        except ValueError:
-            return False
+        a = java_parse_double(a) if isinstance(a, str) else float(a)
+        return a is not None and math.isnan(a)
     if k == "abs":
         a = _eval(node.children[0], row)
         if isinstance(a, str):
-            try:
-                return abs(float(a))
-            except ValueError:
-                return None
+            a = java_parse_double(a)
         return None if a is None else abs(a)
     if k == "nanvl":
         a, b = _eval(node.children[0], row), _eval(node.children[1], row)
@@ -1747,15 +1746,19 @@ def spark_string_to_long(s):
 
 
 _JAVA_DOUBLE = None
+_JAVA_HEX_DOUBLE = None
 
 
 def java_parse_double(s):
-    """java.lang.Double.parseDouble for decimal literals (String.trim of chars <= ' ', optional sign,
-    NaN / Infinity, digits with an optional point, optional exponent, optional f/F/d/D suffix); the value
-    is Python's correctly rounded float() of the same digits. Returns None where Java throws."""
+    """java.lang.Double.parseDouble (String.trim of chars <= ' ', optional sign, NaN / Infinity, digits with an
+    optional point, optional exponent, optional f/F/d/D suffix); the value is Python's correctly rounded float() of
+    the same digits. A hexadecimal floating-point literal (0x h.h p[+-]d, the binary exponent mandatory) is Python's
+    correctly rounded float.fromhex. Returns None where Java throws."""
     import re
-    global _JAVA_DOUBLE
+    global _JAVA_DOUBLE, _JAVA_HEX_DOUBLE
     if _JAVA_DOUBLE is None:
+        _JAVA_HEX_DOUBLE = re.compile(
+            r"([+-]?)0[xX]((?:[0-9a-fA-F]+\.?[0-9a-fA-F]*|\.[0-9a-fA-F]+)[pP][+-]?[0-9]+)[fFdD]?\Z")
         _JAVA_DOUBLE = re.compile(r"([+-]?)(NaN|Infinity|(?:[0-9]+\.?[0-9]*|\.[0-9]+)(?:[eE][+-]?[0-9]+)?)[fFdD]?\Z")
     t = s
     i, j = 0, len(t)
@@ -1763,6 +1766,13 @@ def java_parse_double(s):
         i += 1
     while j > i and ord(t[j - 1]) <= 32:
         j -= 1
+    m = _JAVA_HEX_DOUBLE.match(t[i:j])
+    if m:
+        try:
+            v = float.fromhex("0x" + m.group(2))
+        except OverflowError:
+            v = float("inf")
+        return -v if m.group(1) == "-" else v
     m = _JAVA_DOUBLE.match(t[i:j])
     if not m:
         return None

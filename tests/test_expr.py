@@ -151,3 +151,39 @@ def test_sql_surface_oracle_known_answers():
         for text, want in cases.items():
             got = O._eval(O.OracleParser(text).parse(), row)
             assert got == want, (text, row, got, want)
+
+
+def test_oracle_casts_follow_java_not_python():
+    """CAST in the oracle is Java's, where Python's float() / int() differ: Cast(string -> double) is
+    Double.parseDouble ("inf", "nan", "1_0" throw -> NULL; "Infinity", String.trim and hexadecimal literals are
+    accepted), Cast(string -> long) is UTF8String.toLong (no exponent, no trimming), Cast(double -> long) saturates
+    (NaN -> 0). The implicit string -> double promotion of a comparison takes the same parser."""
+    import math
+    import oracle as O
+    big, small = (1 << 63) - 1, -(1 << 63)
+    cases = [({"item": "1e5"}, {"CAST(item AS BIGINT) IS NULL": True, "CAST(item AS DOUBLE) = 100000": True,
+                                "item = 100000": True}),
+             ({"item": "inf"}, {"CAST(item AS DOUBLE) IS NULL": True, "CAST(item AS BIGINT) IS NULL": True,
+                                "item > 0": None, "isnan(item)": False}),
+             ({"item": "Infinity"}, {"CAST(item AS DOUBLE) > 1e308": True, "CAST(item AS BIGINT) IS NULL": True}),
+             ({"item": "nan"}, {"CAST(item AS DOUBLE) IS NULL": True, "isnan(item)": False}),
+             ({"item": "NaN"}, {"isnan(CAST(item AS DOUBLE))": True, "isnan(item)": True}),
+             ({"item": " 7"}, {"CAST(item AS DOUBLE) = 7": True, "CAST(item AS BIGINT) IS NULL": True}),
+             ({"item": "1_0"}, {"CAST(item AS DOUBLE) IS NULL": True, "CAST(item AS BIGINT) IS NULL": True,
+                                "item = 10": None, "abs(item) = 10": None, "item + 1 = 11": None}),
+             ({"item": "0x1p3"}, {"CAST(item AS DOUBLE) = 8": True, "CAST(item AS DOUBLE) = 0": False}),
+             ({"item": "12.9"}, {"CAST(item AS BIGINT) = 12": True}),
+             ({"att1": 1e19}, {"CAST(att1 AS BIGINT) = %d" % big: True}),
+             ({"att1": -1e19}, {"CAST(att1 AS BIGINT) = %d" % small: True}),
+             ({"att1": float("inf")}, {"CAST(att1 AS BIGINT) = %d" % big: True}),
+             ({"att1": float("-inf")}, {"CAST(att1 AS BIGINT) = %d" % small: True}),
+             ({"att1": float("nan")}, {"CAST(att1 AS BIGINT) = 0": True}),
+             ({"att1": -0.9}, {"CAST(att1 AS BIGINT) = 0": True}),
+             ({"att1": 9223372036854775807.0}, {"CAST(att1 AS BIGINT) = %d" % big: True}),
+             ({"att1": -9223372036854777856.0}, {"CAST(att1 AS BIGINT) = %d" % small: True})]
+    for row, want in cases:
+        row = dict({"item": None, "att1": None, "att2": None}, **row)
+        for text, exp in want.items():
+            got = O._eval(O.OracleParser(text).parse(), row)
+            assert got is exp or (got == exp and type(got) is type(exp)), (text, row, got, exp)
+    assert math.isinf(O._eval(O.OracleParser("CAST(item AS DOUBLE)").parse(), {"item": "-Infinity"}))

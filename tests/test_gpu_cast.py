@@ -1,7 +1,9 @@
 """GPU parity of dq_cast_column (cast.hip + dq_parse.h) against the oracle's restatements of Spark 2.2's
 Cast(string -> long) (UTF8String.toLong) and Cast(string -> double) (java.lang.Double.parseDouble, whose
 correctly rounded value is Python's float() of the same digits). Bar: bit-exact values and identical
-NULLs. Strings with more than 19 significant digits either match or fail loudly (DQ_ERR_UNSUPPORTED)."""
+NULLs. Strings with more than 19 significant digits match where the reference says the device can decide them and
+fail loudly (DQ_ERR_UNSUPPORTED) where it says it cannot; the hard cases (ties, near-midpoints, edges) come from
+tests/number_text_cases.py."""
 import numpy as np
 import pytest
 import torch
@@ -10,6 +12,8 @@ from deequ_amd import engine
 from deequ_amd import native as N
 from deequ_amd.native import NativeError
 from deequ_amd.table import Table, unpack_validity
+import number_text_cases as C
+from number_text_cases import random_numeric_strings
 import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -26,33 +30,6 @@ def gpu_cast(strings, to_type, device=False):
     engine.ctx().cast_column(t["s"].native(), n, to_type, vals.data_ptr(), mask.data_ptr())
     ok = unpack_validity(mask.cpu().numpy(), n)
     return vals.cpu().numpy()[:n], ok, valid
-
-
-def random_numeric_strings(rng, n, max_digits=19):
-    out = []
-    for _ in range(n):
-        k = int(rng.integers(0, 6))
-        nd = int(rng.integers(1, max_digits + 1))
-        digits = "".join(str(d) for d in rng.integers(0, 10, nd))
-        sign = ["", "-", "+", "- ", " "][int(rng.integers(0, 5))]
-        if k == 0:
-            s = sign + digits
-        elif k == 1:
-            p = int(rng.integers(0, nd + 1))
-            s = sign + digits[:p] + "." + digits[p:]
-        elif k == 2:
-            s = sign + digits[:1] + "." + digits[1:] + "e" + str(int(rng.integers(-330, 320)))
-        elif k == 3:
-            s = sign + "0." + "0" * int(rng.integers(0, 30)) + digits
-        elif k == 4:
-            s = sign + digits + ["d", "f", "D", "x", "", "\n", "  "][int(rng.integers(0, 7))]
-        else:
-            s = ["", ".", "-", "+", "NaN", "-Infinity", "Infinity", "1e", "e5", "--1", "1.2.3", " 42 ", "\t7\n",
-                 "9223372036854775807", "9223372036854775808", "-9223372036854775808", "-9223372036854775809",
-                 "1.", ".5", "-.5", "+.", "0.1e-5", "1E+3", "4.9e-324", "2.4703282292062328e-324",
-                 "1.7976931348623157e308", "1.7976931348623159e308", "0x1p3", "007"][int(rng.integers(0, 29))]
-        out.append(s)
-    return out
 
 
 def test_cast_to_long_matches_spark():
@@ -86,21 +63,58 @@ def test_cast_to_double_matches_java(device):
     assert not bad, bad[:10]
 
 
+def _assert_bit_exact(texts, expected, vals, ok):
+    bad = []
+    for i, (s, exp) in enumerate(zip(texts, expected)):
+        if bool(ok[i]) != (exp is not None):
+            bad.append((s, exp, bool(ok[i])))
+        elif exp is not None and not C.same_double(float(vals[i]), exp):
+            bad.append((s, exp, float(vals[i])))
+    assert not bad, (len(bad), bad[:10])
+
+
+@pytest.mark.parametrize("device", [False, True])
+def test_cast_hard_cases_bit_exact(device):
+    """Every hard <= 19-digit case of tests/number_text_cases.py in one call: repr / %.17g of doubles of every binade
+    (subnormals, the lowest and highest binades), 17 / 18 / 19-digit truncations just below and just above the
+    midpoint of adjacent doubles, exact ties (the round-half-to-even branch of el_compute_float), Clinger's
+    multiplications and divisions, and the subnormal / overflow edges. The call must succeed; validity and bits equal
+    Python's correctly rounded float() for every row, and every tie also equals the even neighbour it has by
+    construction. tests/test_number_text_host.py shows the host build of the same header passes all of them, so a
+    failure here is the device build's (__umul64hi, __clzll, the __constant__ table, the fp64 division)."""
+    cases = C.parse_hard_cases(101) + [C.ParseCase(None, None, None)]
+    texts = [c.text for c in cases]
+    vals, ok, _ = gpu_cast(texts, N.TYPE_DOUBLE, device=device)
+    _assert_bit_exact(texts, [c.expected for c in cases], vals, ok)
+    ties = [(c, float(vals[i])) for i, c in enumerate(cases) if c.tie is not None]
+    assert len(ties) >= 300
+    bad = [(c, v) for c, v in ties if not C.same_double(v, c.tie)]
+    assert not bad, (len(bad), bad[:10])
+
+
 def test_cast_long_significands_match_or_fail_loudly():
-    rng = np.random.default_rng(5)
-    strings = random_numeric_strings(rng, 3000, max_digits=30)
-    strings = [s for s in strings if s != "0x1p3"]
-    try:
-        vals, ok, _ = gpu_cast(strings, N.TYPE_DOUBLE)
-    except NativeError:
-        return
-    for i, s in enumerate(strings):
-        exp = O.java_parse_double(s)
-        assert bool(ok[i]) == (exp is not None), s
-        if exp is not None and not np.isnan(exp):
-            assert np.float64(vals[i]).view(np.uint64) == np.float64(exp).view(np.uint64), s
+    """Strings of 20 to 40 significant digits, labelled by the reference alone (tests/number_text_cases.py): where the
+    first 19 digits w and w + 1 round alike (`decidable`) the call succeeds with Java's bits for every row; a string
+    on a rounding boundary (the exact decimal expansions of midpoints, also with a late digit changed) or a well-formed
+    hexadecimal literal fails the call loudly, all in one call and one per call; a malformed hexadecimal literal is
+    NULL without an error."""
+    cases = C.parse_long_cases(102)
+    decidable = [c for c in cases if c.label == "decidable"]
+    boundary = [c for c in cases if c.label == "boundary"]
+    null = [c for c in cases if c.label == "null"]
+    assert len(decidable) >= 500 and len(boundary) >= 50 and len(null) == 3
+    texts = [c.text for c in decidable]
+    vals, ok, _ = gpu_cast(texts, N.TYPE_DOUBLE)
+    _assert_bit_exact(texts, [c.expected for c in decidable], vals, ok)
     with pytest.raises(NativeError):
-        gpu_cast(["0x1p3"], N.TYPE_DOUBLE)
+        gpu_cast([c.text for c in boundary], N.TYPE_DOUBLE)
+    hexes = [c for c in boundary if "x" in c.text.lower()]
+    assert len(hexes) == 3
+    for c in boundary[::max(1, len(boundary) // 17)] + hexes:
+        with pytest.raises(NativeError):
+            gpu_cast(["1.5", c.text, "2"], N.TYPE_DOUBLE)
+    vals, ok, _ = gpu_cast([c.text for c in null] + ["1.5"], N.TYPE_DOUBLE)
+    assert list(ok) == [False, False, False, True] and vals[3] == 1.5
 
 
 def test_cast_empty_and_all_null():
