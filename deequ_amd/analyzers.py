@@ -80,6 +80,45 @@ class Preconditions:
         return check
 
 
+WIDE_DECIMAL_OPS = (N.OP_COMPLETENESS, N.OP_SUM, N.OP_MEAN, N.OP_MINIMUM, N.OP_MAXIMUM, N.OP_STANDARD_DEVIATION,
+                    N.OP_APPROX_COUNT_DISTINCT)
+
+
+def wide_decimal_columns(data, columns):
+    """The names among `columns` that are 128-bit decimal columns (DQ_TYPE_DECIMAL128) of `data`."""
+    out = []
+    for c in columns:
+        try:
+            col = data[c] if c in data else None
+        except (KeyError, TypeError):
+            col = None
+        if col is not None and getattr(col, "spark_type", None) == N.TYPE_DECIMAL128:
+            out.append(c)
+    return out
+
+
+def reject_wide_decimals(data, columns, what):
+    """Only the fused scan's seven ops (and the cast) read a 128-bit decimal column: anything else fails alone."""
+    wide = wide_decimal_columns(data, columns)
+    if wide:
+        raise UnsupportedOnDevice(
+            "%s over %s column %s: a decimal of more than 18 digits supports Completeness, Sum, Mean, Minimum, "
+            "Maximum, StandardDeviation and ApproxCountDistinct only" % (what, data[wide[0]].type_name, wide[0]))
+
+
+def analyzer_columns(analyzer):
+    """The columns an analyzer names as its inputs (not those of its `where` / predicate)."""
+    cols = []
+    for f in ("column", "firstColumn", "secondColumn"):
+        v = getattr(analyzer, f, None)
+        if isinstance(v, str):
+            cols.append(v)
+    v = getattr(analyzer, "columns", None)
+    if isinstance(v, (list, tuple)):
+        cols.extend(c for c in v if isinstance(c, str))
+    return cols
+
+
 def entityFrom(columns):
     return Entity.Column if len(columns) == 1 else Entity.Mutlicolumn
 
@@ -588,6 +627,7 @@ class KLLSketch(ScanShareableAnalyzer):
 
     def computeStateFrom(self, data):
         from .runners import KLLRunner
+        reject_wide_decimals(data, [self.column], "KLLSketch")
         return KLLRunner.sketch_column(data, self.column, self.sketchSize, self.shrinkingFactor)
 
     def computeMetricFrom(self, state):
@@ -838,6 +878,7 @@ def _block_from_dict(freq, like):
 
 def computeFrequencies(data, groupingColumns, include_nulls=False):
     """FrequencyBasedAnalyzer.computeFrequencies (A/GroupingAnalyzers.scala:53-79) on the GPU."""
+    reject_wide_decimals(data, groupingColumns, "a grouping")
     table = engine.frequencies(data, list(groupingColumns), include_nulls=include_nulls)
     return FrequenciesAndNumRows(table, table.num_rows, list(groupingColumns))
 
@@ -1018,6 +1059,7 @@ class Histogram(Analyzer):
         return [param_check, Preconditions.hasColumn(self.column)]
 
     def computeStateFrom(self, data):
+        reject_wide_decimals(data, [self.column], "Histogram")
         if self.binningUdf is not None:
             return FrequenciesAndNumRows(self.binned_counts(data), data.count(), [self.column])
         table = engine.frequencies(data, [self.column], include_nulls=True)

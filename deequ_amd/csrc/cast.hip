@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "dq_common.h"
+#include "dq_dec128.h"
 #include "dq_device.h"
 #include "dq_internal.h"
 #include "dq_parse.h"
@@ -210,6 +211,33 @@ cast_kernel(CastSource c, int64_t nrows, int to_double, void* __restrict__ value
     }
 }
 
+// DECIMAL128 source (16-byte cells): Decimal.toDouble / Decimal.toLong of every row with the scan's own device
+// functions (dq_dec128.h) -- the bit-exact window on the per-row conversion. One lane per row, one 16-byte load.
+__global__ void __launch_bounds__(kCastBlock)
+cast_dec128_kernel(const uint4* __restrict__ cells, const uint64_t* __restrict__ validity, int scale, int64_t nrows,
+                   int to_double, void* __restrict__ values_out, uint64_t* __restrict__ validity_out) {
+    const Dec128Scale sc = dec128_scale(scale);
+    const int64_t stride = (int64_t)gridDim.x * kCastBlock;
+    for (int64_t base = (int64_t)blockIdx.x * kCastBlock; base < nrows; base += stride) {
+        const int64_t r = base + threadIdx.x;
+        const bool ok = r < nrows && row_valid(validity, r);
+        double d = 0.0;
+        int64_t v = 0;
+        if (ok) {
+            const uint4 c = cells[r];
+            const uint64_t lo = ((uint64_t)c.y << 32) | c.x, hi = ((uint64_t)c.w << 32) | c.z;
+            if (to_double) d = dec128_to_double_scaled(lo, hi, sc);
+            else v = dec128_to_long_scaled(lo, hi, sc);
+        }
+        if (r < nrows) {
+            if (to_double) static_cast<double*>(values_out)[r] = d;
+            else static_cast<int64_t*>(values_out)[r] = v;
+        }
+        const unsigned long long ball = __ballot(ok);
+        if ((threadIdx.x & 63) == 0 && r < nrows) validity_out[r >> 6] = ball;
+    }
+}
+
 }  // namespace dq
 
 extern "C" {
@@ -226,6 +254,8 @@ int dq_cast_column(dq_ctx* ctx, const dq_column* column, int64_t nrows, int32_t 
     // multi-device context: host column in, host results out; each device casts its contiguous row shard (2048-row
     // aligned, so its validity words start on a word boundary) and copies its slice of the results back
     if (column->flags & DQ_COL_DEVICE) return dq::ctx_fail(ctx, DQ_ERR_UNSUPPORTED, "a multi-device context takes host columns");
+    if (column->spark_type == DQ_TYPE_DECIMAL128)
+        return dq::ctx_fail(ctx, DQ_ERR_UNSUPPORTED, "dq_cast_column: DECIMAL128 columns need a single-device context");
     std::vector<int> rc(nsub, DQ_OK);
     std::vector<std::string> err(nsub);
     std::vector<dq_column> cols(nsub, *column);
@@ -265,9 +295,15 @@ static int cast_single(dq_ctx* ctx, const dq_column* column, int64_t nrows, int3
                        uint8_t* validity_dev) {
     const int t = column->spark_type;
     const bool is_string = t == DQ_TYPE_STRING;
+    const bool is_wide = t == DQ_TYPE_DECIMAL128;
+    if (is_wide && (column->decimal_precision < 19 || column->decimal_precision > 38 || column->decimal_scale < 0 ||
+                    column->decimal_scale > column->decimal_precision))
+        return dq::ctx_fail(ctx, DQ_ERR_UNSUPPORTED, "dq_cast_column: DECIMAL128 needs 19 <= precision <= 38 and 0 <= scale <= precision");
+    if (is_wide && (column->flags & DQ_COL_DEVICE) && nrows > 0 && (((uintptr_t)column->values & 15) || ((uintptr_t)column->validity & 7)))
+        return dq::ctx_fail(ctx, DQ_ERR_ALIGNMENT, "dq_cast_column: DECIMAL128 values must be 16-byte and validity 8-byte aligned");
     if (is_string && !column->offsets)
         return dq::ctx_fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_cast_column: string column without offsets");
-    if (!is_string && !(t == DQ_TYPE_BOOLEAN || t == DQ_TYPE_BYTE || t == DQ_TYPE_SHORT || t == DQ_TYPE_INT ||
+    if (!is_string && !is_wide && !(t == DQ_TYPE_BOOLEAN || t == DQ_TYPE_BYTE || t == DQ_TYPE_SHORT || t == DQ_TYPE_INT ||
                         t == DQ_TYPE_LONG || t == DQ_TYPE_FLOAT || t == DQ_TYPE_DOUBLE || t == DQ_TYPE_DECIMAL))
         return dq::ctx_fail(ctx, DQ_ERR_UNSUPPORTED, "dq_cast_column: source type cannot be cast to a number here");
     if (t == DQ_TYPE_DECIMAL && (column->decimal_precision > 18 || column->decimal_scale < 0 || column->decimal_scale > 18))
@@ -302,7 +338,7 @@ static int cast_single(dq_ctx* ctx, const dq_column* column, int64_t nrows, int3
             if (total > 0) DQ_CTX_HIP(ctx, hipMemcpyAsync(b, column->values, (size_t)total, hipMemcpyHostToDevice, s));
             DQ_CTX_HIP(ctx, hipMemcpyAsync(o, column->offsets, sizeof(int32_t) * (size_t)(nrows + 1), hipMemcpyHostToDevice, s));
         } else {
-            const size_t vb = (size_t)nrows * dq::elem_size(c.elem);
+            const size_t vb = (size_t)nrows * (is_wide ? 16 : dq::elem_size(c.elem));
             DQ_CTX_HIP(ctx, buf.alloc(&b, vb));
             DQ_CTX_HIP(ctx, hipMemcpyAsync(b, column->values, vb, hipMemcpyHostToDevice, s));
         }
@@ -324,7 +360,10 @@ static int cast_single(dq_ctx* ctx, const dq_column* column, int64_t nrows, int3
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(blocks, (int64_t)dq::ctx_cus(ctx) * 16));
     const int to_double = to_type == DQ_TYPE_DOUBLE ? 1 : 0;
     const int no_short = getenv("DQ_CAST_NO_SHORT") ? 1 : 0;  // A/B and tests: every row through dq_parse.h
-    if (is_string)
+    if (is_wide)
+        hipLaunchKernelGGL(dq::cast_dec128_kernel, dim3(grid), dim3(dq::kCastBlock), 0, s, (const uint4*)c.values, c.validity,
+                           column->decimal_scale, nrows, to_double, values_dev, (uint64_t*)validity_dev);
+    else if (is_string)
         hipLaunchKernelGGL(dq::cast_kernel<true>, dim3(grid), dim3(dq::kCastBlock), 0, s, c, nrows, to_double, values_dev,
                            (uint64_t*)validity_dev, dslow, no_short);
     else

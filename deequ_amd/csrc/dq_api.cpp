@@ -557,6 +557,8 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
         if (flags & DQ_SCAN_OUT_DEVICE)
             return fail(ctx, DQ_ERR_UNSUPPORTED, "a multi-device context returns host states (no DQ_SCAN_OUT_DEVICE)");
         for (int c = 0; c < ncols; ++c) {
+            if (columns[c].spark_type == DQ_TYPE_DECIMAL128)
+                return fail(ctx, DQ_ERR_UNSUPPORTED, "column %d: DECIMAL128 columns need a single-device context", c);
             if (columns[c].flags & DQ_COL_DEVICE)
                 return fail(ctx, DQ_ERR_UNSUPPORTED, "device columns of a multi-device context go through dq_scan_sharded");
             if (columns[c].length != nrows)
@@ -584,8 +586,12 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
         if (col.length != nrows)
             return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "column %d has %lld rows, batch has %lld", c,
                         (long long)col.length, (long long)nrows);
-        if (col.spark_type < DQ_TYPE_BOOLEAN || col.spark_type > DQ_TYPE_DECIMAL)
+        if (col.spark_type < DQ_TYPE_BOOLEAN || col.spark_type > DQ_TYPE_DECIMAL128)
             return fail(ctx, DQ_ERR_UNSUPPORTED, "column %d: unknown spark type %d", c, col.spark_type);
+        const bool wide = col.spark_type == DQ_TYPE_DECIMAL128;
+        if (wide && (col.decimal_precision < 19 || col.decimal_precision > 38 || col.decimal_scale < 0 ||
+                     col.decimal_scale > col.decimal_precision))
+            return fail(ctx, DQ_ERR_UNSUPPORTED, "column %d: DECIMAL128 needs 19 <= precision <= 38 and 0 <= scale <= precision", c);
         if (col.spark_type == DQ_TYPE_STRING && nrows > 0 && !col.offsets)
             return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "string column %d without offsets", c);
         if (col.flags & DQ_COL_OFFSETS64)
@@ -595,7 +601,7 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
         if ((col.flags & DQ_COL_DEVICE) && nrows > 0) {
             const int e = elem_of(col.spark_type);
             // strings: 4-byte aligned UTF-8 (read as dwords), padded by 16 bytes past offsets[length]
-            const size_t va = e == ET_NONE ? 4 : (elem_size(e) == 1 ? 8 : 16);
+            const size_t va = wide ? 16 : (e == ET_NONE ? 4 : (elem_size(e) == 1 ? 8 : 16));
             if (((uintptr_t)col.values % va) != 0 || ((uintptr_t)col.validity % 8) != 0)
                 return fail(ctx, DQ_ERR_ALIGNMENT, "device column %d: values must be %zu-byte and validity 8-byte aligned", c, va);
         }
@@ -603,10 +609,26 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
     auto col_ok = [&](int c) { return c >= 0 && c < ncols; };
     std::vector<char> pred_used(npreds, 0);
     std::vector<char> col_used(ncols, 0);
+    // ops over a DECIMAL128 column: answered by the decimal128 launch, never by a value / bits / string slot
+    std::vector<char> wide_op(nops, 0);
     for (int i = 0; i < nops; ++i) {
         const dq_op& op = ops[i];
         if (op.where >= npreds || op.where < -1) return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "op %d: bad where index", i);
         if (op.where >= 0) pred_used[op.where] = 1;
+        if (op.kind != DQ_OP_SIZE && op.kind != DQ_OP_COMPLIANCE) {
+            const bool w0 = col_ok(op.column[0]) && columns[op.column[0]].spark_type == DQ_TYPE_DECIMAL128;
+            const bool w1 = op.kind == DQ_OP_CORRELATION && col_ok(op.column[1]) &&
+                            columns[op.column[1]].spark_type == DQ_TYPE_DECIMAL128;
+            if (w0 || w1) {
+                const bool ok = op.kind == DQ_OP_COMPLETENESS || op.kind == DQ_OP_MEAN || op.kind == DQ_OP_SUM ||
+                                op.kind == DQ_OP_MINIMUM || op.kind == DQ_OP_MAXIMUM ||
+                                op.kind == DQ_OP_STANDARD_DEVIATION || op.kind == DQ_OP_APPROX_COUNT_DISTINCT;
+                if (!ok) return fail(ctx, DQ_ERR_UNSUPPORTED, "op %d: kind %d is not supported over a DECIMAL128 column", i, op.kind);
+                wide_op[i] = 1;
+                col_used[op.column[0]] = 1;
+                continue;
+            }
+        }
         switch (op.kind) {
             case DQ_OP_SIZE: break;
             case DQ_OP_COMPLIANCE:
@@ -672,6 +694,8 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
             const int op = pr.code[k], arg = pr.code[k + 1];
             if (op == DQ_P_COL) {
                 if (!col_ok(arg)) return fail(ctx, DQ_ERR_PREDICATE, "predicate %d: bad column %d", p, arg);
+                if (columns[arg].spark_type == DQ_TYPE_DECIMAL128)
+                    return fail(ctx, DQ_ERR_UNSUPPORTED, "predicate %d: a predicate cannot read DECIMAL128 column %d", p, arg);
                 col_used[arg] = 1;
                 ++depth;
             } else if (op == DQ_P_CONST || op == DQ_P_NULL) {
@@ -721,6 +745,7 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
     std::vector<int> fused_col(nops, -1);     // Compliance ops answered inside a value slot
     for (int i = 0; i < nops; ++i) {
         const dq_op& op = ops[i];
+        if (wide_op[i]) continue;
         const auto key = std::make_pair(op.column[0], op.where);
         switch (op.kind) {
             case DQ_OP_MEAN: case DQ_OP_SUM: case DQ_OP_MINIMUM: case DQ_OP_MAXIMUM: uses[key].flags |= CF_STATS; break;
@@ -834,6 +859,7 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
     std::vector<int> op_sslot(nops, -1);
     for (int i = 0; i < nops; ++i) {
         const dq_op& op = ops[i];
+        if (wide_op[i]) continue;
         const bool str_hll = op.kind == DQ_OP_APPROX_COUNT_DISTINCT && columns[op.column[0]].spark_type == DQ_TYPE_STRING;
         if (!(op.kind == DQ_OP_MIN_LENGTH || op.kind == DQ_OP_MAX_LENGTH || op.kind == DQ_OP_DATATYPE || str_hll)) continue;
         const auto key = std::make_pair(op.column[0], op.where);
@@ -868,6 +894,49 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
         m.pad = 0;
         sopmap.push_back(m);
     }
+
+    // DECIMAL128 ops -> decimal128 slots (column, where), one launch for all of them (decimal128.hip).
+    std::vector<D128Slot> dslots128;
+    std::map<std::pair<int, int>, int> dslot_of;
+    std::vector<D128OpMap> dopmap;
+    std::vector<int> op_dslot(nops, -1);
+    for (int i = 0; i < nops; ++i) {
+        if (!wide_op[i]) continue;
+        const dq_op& op = ops[i];
+        const auto key = std::make_pair(op.column[0], op.where);
+        auto it = dslot_of.find(key);
+        if (it == dslot_of.end()) {
+            D128Slot ds;
+            memset(&ds, 0, sizeof(ds));
+            ds.hll_slot = -1;
+            ds.scale = columns[op.column[0]].decimal_scale;
+            ds.values = (const void*)(intptr_t)op.column[0];  // column index until pointers are known
+            ds.where_t = (const uint64_t*)(intptr_t)(op.where + 1);
+            dslots128.push_back(ds);
+            it = dslot_of.emplace(key, (int)dslots128.size() - 1).first;
+        }
+        D128Slot& ds = dslots128[it->second];
+        op_dslot[i] = it->second;
+        switch (op.kind) {
+            case DQ_OP_MEAN: case DQ_OP_SUM: ds.flags |= DF_SUM; break;
+            case DQ_OP_MINIMUM: case DQ_OP_MAXIMUM: ds.flags |= DF_MINMAX; break;
+            case DQ_OP_STANDARD_DEVIATION: ds.flags |= DF_MOMENTS; break;
+            case DQ_OP_APPROX_COUNT_DISTINCT:
+                ds.flags |= DF_HLL;
+                if (ds.hll_slot < 0) ds.hll_slot = nhll++;
+                break;
+            default: break;
+        }
+        if (op.kind != DQ_OP_APPROX_COUNT_DISTINCT) {  // the HLL state is packed by finalize_kernel
+            D128OpMap m;
+            m.op = i;
+            m.kind = op.kind;
+            m.slot = it->second;
+            m.has_where = op.where >= 0;
+            dopmap.push_back(m);
+        }
+    }
+    const int ndslots = (int)dslots128.size();
 
     // `where` filters evaluated inside the scan (WhereOut, dq_internal.h): every simple predicate used as a `where`
     // (DQ_WHERE_MASKS=0 or DQ_PRED_VM=1: the bitmap pass for all of them, for A/B runs).
@@ -915,6 +984,10 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
             m.decimal_scale = t == DQ_TYPE_DECIMAL ? columns[c].decimal_scale : 0;
         }
         m.wslot = -1;
+        if (wide_op[i]) {  // written by finalize_decimal128_kernel; the HLL words by finalize_kernel
+            if (op.kind == DQ_OP_APPROX_COUNT_DISTINCT) m.hll_slot = dslots128[op_dslot[i]].hll_slot;
+            continue;
+        }
         const bool masked_where = op.where >= 0 && wmasked[op.where];
         switch (op.kind) {
             case DQ_OP_SIZE:
@@ -1012,6 +1085,8 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
         }
         for (const StrSlot& ss : sslots)
             if ((int)(intptr_t)ss.where_t - 1 == p) wp.bitmaps = true;
+        for (const D128Slot& ds : dslots128)
+            if ((int)(intptr_t)ds.where_t - 1 == p) wp.bitmaps = true;
         if ((int)wp.mask_col.size() > kWhereMasks) {  // too many consumers for one producer: the bitmap pass
             wmasked[p] = 0;
             wp = WherePlan();
@@ -1130,6 +1205,9 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
     int sgrid = nsslots ? string_scan_grid(ctx->cus, nrows) : 0;
     if (concurrent && sgrid) sgrid = std::max(1, (sgrid + nlaunch - 1) / nlaunch);
     gstride = std::max(gstride, sgrid);
+    // the decimal128 launch runs on the ctx stream after the other launches joined: the whole chip
+    const int dgrid = ndslots ? decimal128_scan_grid(ctx->cus, nrows) : 0;
+    gstride = std::max(gstride, dgrid);
     // producers first: their masks are read by the other launches
     std::stable_sort(groups.begin(), groups.end(), [](const Group& a, const Group& b) { return (a.heavy == 3) > (b.heavy == 3); });
     std::vector<int32_t> slot_nblocks(std::max<size_t>(slots.size(), 1), 1);
@@ -1144,6 +1222,8 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
         if (kv.second.hll >= 0) hll_nblocks[kv.second.hll] = slot_nblocks[kv.second.slot];
     for (const StrSlot& ss : sslots)
         if (ss.hll_slot >= 0) hll_nblocks[ss.hll_slot] = sgrid;
+    for (const D128Slot& ds : dslots128)
+        if (ds.hll_slot >= 0) hll_nblocks[ds.hll_slot] = dgrid;
     const int64_t pwords = padded_words_for(nrows);
     const size_t bitmap_bytes = (size_t)(nrows + 7) / 8;
 
@@ -1166,6 +1246,7 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
             }
             size_t vbytes;
             if (col.spark_type == DQ_TYPE_STRING) vbytes = nrows > 0 ? (size_t)col.offsets[nrows] : 0;
+            else if (col.spark_type == DQ_TYPE_DECIMAL128) vbytes = (size_t)nrows * 16;
             else vbytes = (size_t)nrows * elem_size(elem_of(col.spark_type));
             void* v = b.take(vbytes + 16);
             void* vd = col.validity ? b.take(align_up(bitmap_bytes, 8) + 8) : nullptr;
@@ -1217,12 +1298,16 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
         StrSlot* dsslots = (StrSlot*)b.take(sizeof(StrSlot) * std::max(nsslots, 1));
         StrPartial* spartials = (StrPartial*)b.take(sizeof(StrPartial) * (size_t)std::max(nsslots, 1) * gstride);
         StrOpMap* dsops = (StrOpMap*)b.take(sizeof(StrOpMap) * std::max<size_t>(sopmap.size(), 1));
+        D128Slot* ddslots = (D128Slot*)b.take(sizeof(D128Slot) * std::max(ndslots, 1));
+        D128Partial* dpartials = (D128Partial*)b.take(sizeof(D128Partial) * (size_t)std::max(ndslots, 1) * gstride);
+        D128OpMap* ddops = (D128OpMap*)b.take(sizeof(D128OpMap) * std::max<size_t>(dopmap.size(), 1));
         if (!pass) {
             arena_need = b.off;
             int rc = ensure_arena(ctx, arena_need);
             if (rc) return rc;
             // plan bytes uploaded through pinned staging
-            size_t pin = sizeof(int32_t) * std::max(npreds, 1) + 32 + sizeof(StrSlot) * std::max(nsslots, 1) + sizeof(StrOpMap) * std::max<size_t>(sopmap.size(), 1) +
+            size_t pin = sizeof(D128Slot) * std::max(ndslots, 1) + sizeof(D128OpMap) * std::max<size_t>(dopmap.size(), 1) + 64 +
+                         sizeof(int32_t) * std::max(npreds, 1) + 32 + sizeof(StrSlot) * std::max(nsslots, 1) + sizeof(StrOpMap) * std::max<size_t>(sopmap.size(), 1) +
                          sizeof(PredColumn) * std::max(ncols, 1) + sizeof(SlotDesc) * std::max(nslots, 1) +
                          sizeof(OpMap) * nops + sizeof(dq_state) * nops + 4 * (slot_nblocks.size() + hll_nblocks.size() + nslots) + 8192;
             for (int p = 0; p < npreds; ++p)
@@ -1428,11 +1513,26 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
             DQ_HIP(ctx, hipEventRecord(ctx->join_ev[j], ctx->side[j]));
             DQ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->join_ev[j], 0));
         }
+        if (ndslots) {
+            for (D128Slot& ds : dslots128) {
+                const int c = (int)(intptr_t)ds.values;
+                const int w = (int)(intptr_t)ds.where_t - 1;
+                ds.values = dval[c];
+                ds.validity = (const uint64_t*)dvalid[c];
+                ds.where_t = w >= 0 ? pt[w] : nullptr;
+                ds.where_nn = w >= 0 ? pn[w] : nullptr;
+            }
+            rc = upload(ddslots, dslots128.data(), sizeof(D128Slot) * ndslots);
+            if (rc) return rc;
+            launch_decimal128_scan(ddslots, ndslots, nrows, dgrid, gstride, dpartials, hllp, ctx->stream);
+            DQ_HIP(ctx, hipGetLastError());
+            ctx->kernel_launches[DQ_KERNEL_DECIMAL128]++;
+        }
         if (nslots) {
             launch_reduce_partials(partials, dslot_nb, nslots, gstride, finals, ctx->stream);
             DQ_HIP(ctx, hipGetLastError());
         }
-        if (nslots || nsslots) ctx->scan_launches++;
+        if (nslots || nsslots || ndslots) ctx->scan_launches++;
         if (nhll) {
             rc = upload(dhll_nb, hll_nblocks.data(), sizeof(int32_t) * hll_nblocks.size());
             if (rc) return rc;
@@ -1445,6 +1545,13 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
             rc = upload(dsops, sopmap.data(), sizeof(StrOpMap) * sopmap.size());
             if (rc) return rc;
             launch_finalize_strings(dsops, (int)sopmap.size(), spartials, sgrid, gstride, nrows, dout, ctx->stream);
+            DQ_HIP(ctx, hipGetLastError());
+        }
+        if (!dopmap.empty()) {
+            rc = upload(ddops, dopmap.data(), sizeof(D128OpMap) * dopmap.size());
+            if (rc) return rc;
+            launch_finalize_decimal128(ddslots, ndslots, ddops, (int)dopmap.size(), dpartials, dgrid, gstride, nrows, dout,
+                                       ctx->stream);
             DQ_HIP(ctx, hipGetLastError());
         }
         if (any_status) {
@@ -1487,10 +1594,13 @@ int dq_scan_streamed(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t n
         return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_scan_streamed: invalid arguments");
     ctx->err.clear();
     if (!ctx->subs.empty()) return fail(ctx, DQ_ERR_UNSUPPORTED, "dq_scan_streamed takes a single-device context");
-    for (int c = 0; c < ncols; ++c)
+    for (int c = 0; c < ncols; ++c) {
         if ((columns[c].flags & DQ_COL_DEVICE) || columns[c].length != nrows)
             return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_scan_streamed: column %d must be a host column of %lld rows", c,
                         (long long)nrows);
+        if (columns[c].spark_type == DQ_TYPE_DECIMAL128)
+            return fail(ctx, DQ_ERR_UNSUPPORTED, "dq_scan_streamed: column %d: DECIMAL128 columns go through dq_scan", c);
+    }
     if (nops == 0) return DQ_OK;
     chunk_rows = std::max<int64_t>(kTileRows, chunk_rows / kTileRows * kTileRows);
     if (nrows <= chunk_rows) return dq_scan(ctx, columns, ncols, nrows, ops, nops, preds, npreds, out, 0);

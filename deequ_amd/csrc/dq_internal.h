@@ -151,6 +151,44 @@ struct StrOpMap {
     int32_t pad;
 };
 
+// DECIMAL128 columns (decimal128.hip): one slot per (column, where); one launch covers every slot of a call.
+enum D128Flags : uint32_t {
+    DF_SUM = 1u,      // exact 192-bit sum (Sum, Mean)
+    DF_MINMAX = 2u,   // signed 128-bit extremes
+    DF_MOMENTS = 4u,  // (n, avg, m2) over dec128_to_double of each row
+    DF_HLL = 8u,      // HLL++ registers of dec128_spark_hash
+};
+constexpr int kD128WordsPerWave = 4;                                 // 64-row steps a wave issues together
+constexpr int kD128TileRows = (kBlock / 64) * kD128WordsPerWave * 64;  // 1024 rows per workgroup per step
+
+struct D128Slot {
+    const void* values;        // 16-byte cells, 16-byte aligned
+    const uint64_t* validity;  // nullptr = all valid (exactly ceil(nrows / 8) bytes are read)
+    const uint64_t* where_t;   // where TRUE (padded bitmap) or nullptr
+    const uint64_t* where_nn;  // where NOT NULL
+    uint32_t flags;            // D128Flags
+    int32_t hll_slot;          // shared numbering with the other HLL partials, -1 = none
+    int32_t scale;
+    int32_t pad;
+};
+
+struct D128Partial {
+    int64_t n;                 // rows non-NULL and where TRUE
+    int64_t wt, wnn;           // rows with where TRUE / NOT NULL (all rows without a where)
+    int64_t mcount;            // rows behind (mean, m2): n when DF_MOMENTS
+    uint64_t sum[3];           // 192-bit two's-complement sum of the unscaled values
+    uint64_t minlo, minhi, maxlo, maxhi;
+    double mean, m2;
+    int64_t mom[32];           // DF_MOMENTS: digit counters of the exact sums of x and x^2 (dq_dec128.h moment_digits)
+};
+
+struct D128OpMap {
+    int32_t op;                // index into the dq_state output
+    int32_t kind;              // dq_op_kind
+    int32_t slot;
+    int32_t has_where;
+};
+
 // Predicate VM limits.
 constexpr int kPredStack = 16;
 
@@ -398,6 +436,12 @@ void launch_string_scan(const StrSlot* slots, int nslots, int64_t nrows, int gri
                         uint8_t* hll_partials, hipStream_t s);
 void launch_finalize_strings(const StrOpMap* ops, int nops, const StrPartial* partials, int nblocks, int gstride,
                              int64_t nrows, dq_state* out, hipStream_t s);
+int decimal128_scan_grid(int cus, int64_t nrows);
+void launch_decimal128_scan(const D128Slot* slots, int nslots, int64_t nrows, int grid, int gstride,
+                            D128Partial* partials, uint8_t* hll_partials, hipStream_t s);
+void launch_finalize_decimal128(const D128Slot* slots, int nslots, const D128OpMap* ops, int nops,
+                                const D128Partial* partials, int nblocks, int gstride, int64_t nrows, dq_state* out,
+                                hipStream_t s);
 void launch_regex(const PredColumn& col, const int32_t* image_dev, int64_t nrows, int64_t padded_words,
                   uint64_t* out_t, uint64_t* out_nn, int32_t* status, hipStream_t s);
 void launch_synth_column(int kind, uint64_t seed, int64_t row0, int64_t nrows, void* out, hipStream_t s);

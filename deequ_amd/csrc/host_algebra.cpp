@@ -10,6 +10,7 @@
 
 #include "../../include/dq.h"
 #include "dq_common.h"
+#include "dq_dec128.h"
 #include "hll_bias_p9.h"
 
 namespace dq {
@@ -53,8 +54,19 @@ double java_math_max(double a, double b) {
 }
 
 
+// Wide (DECIMAL128) Sum / Mean partials: add the 192-bit limbs, then one conversion of the total.
+double wide_sum_merge(const uint64_t* a, const uint64_t* b, int scale, uint64_t* out, int32_t* overflow) {
+    Acc192 x, y;
+    for (int i = 0; i < 3; ++i) { x.w[i] = a[i]; y.w[i] = b[i]; }
+    acc192_add(x, y);
+    for (int i = 0; i < 3; ++i) out[i] = x.w[i];
+    *overflow = acc192_overflows_38(x) ? 1 : 0;
+    return *overflow ? NAN : dec128_to_double(x.w[0], x.w[1], scale);
+}
+
 int cell_bytes(int spark_type) {
     switch (spark_type) {
+        case DQ_TYPE_DECIMAL128: return 16;
         case DQ_TYPE_BOOLEAN: case DQ_TYPE_BYTE: return 1;
         case DQ_TYPE_SHORT: return 2;
         case DQ_TYPE_INT: case DQ_TYPE_DATE: case DQ_TYPE_FLOAT: return 4;
@@ -115,7 +127,10 @@ int dq_state_merge(const dq_state* a, const dq_state* b, dq_state* out) {
             break;
         case DQ_OP_MEAN:
             r.u.mean.count = a->u.mean.count + b->u.mean.count;
-            if (a->u.mean.exact && b->u.mean.exact) {  // Long partials: wrap-around add, one final cast
+            if (a->u.mean.exact == 2 && b->u.mean.exact == 2 && a->u.mean.wscale == b->u.mean.wscale) {
+                r.u.mean.sum = wide_sum_merge(a->u.mean.wsum, b->u.mean.wsum, a->u.mean.wscale, r.u.mean.wsum,
+                                              &r.u.mean.woverflow);
+            } else if (a->u.mean.exact == 1 && b->u.mean.exact == 1) {  // Long partials: wrap-around add, one final cast
                 r.u.mean.isum = (int64_t)((uint64_t)a->u.mean.isum + (uint64_t)b->u.mean.isum);
                 r.u.mean.sum = (double)r.u.mean.isum;
             } else {
@@ -124,7 +139,10 @@ int dq_state_merge(const dq_state* a, const dq_state* b, dq_state* out) {
             }
             break;
         case DQ_OP_SUM:
-            if (a->u.dbl.exact && b->u.dbl.exact) {
+            if (a->u.dbl.exact == 2 && b->u.dbl.exact == 2 && a->u.dbl.wscale == b->u.dbl.wscale) {
+                r.u.dbl.value = wide_sum_merge(a->u.dbl.wsum, b->u.dbl.wsum, a->u.dbl.wscale, r.u.dbl.wsum,
+                                               &r.u.dbl.woverflow);
+            } else if (a->u.dbl.exact == 1 && b->u.dbl.exact == 1) {
                 r.u.dbl.isum = (int64_t)((uint64_t)a->u.dbl.isum + (uint64_t)b->u.dbl.isum);
                 r.u.dbl.value = (double)r.u.dbl.isum;
             } else {
@@ -148,6 +166,21 @@ int dq_state_merge(const dq_state* a, const dq_state* b, dq_state* out) {
             r.u.stddev.n = newN;
             r.u.stddev.avg = a->u.stddev.avg + deltaN * on;
             r.u.stddev.m2 = a->u.stddev.m2 + b->u.stddev.m2 + delta * deltaN * n * on;
+            r.u.stddev.exact = (a->u.stddev.exact == 1 && b->u.stddev.exact == 1) ? 1 : 0;
+            if (r.u.stddev.exact) {  // the exact sums of x and x^2: multi-limb two's-complement adds
+                uint64_t carry = 0;
+                for (int i = 0; i < 6; ++i) {
+                    const u128 t = (u128)a->u.stddev.xs1[i] + b->u.stddev.xs1[i] + carry;
+                    r.u.stddev.xs1[i] = (uint64_t)t;
+                    carry = (uint64_t)(t >> 64);
+                }
+                carry = 0;
+                for (int i = 0; i < 11; ++i) {
+                    const u128 t = (u128)a->u.stddev.xs2[i] + b->u.stddev.xs2[i] + carry;
+                    r.u.stddev.xs2[i] = (uint64_t)t;
+                    carry = (uint64_t)(t >> 64);
+                }
+            }
             break;
         }
         case DQ_OP_CORRELATION: {  // A/Correlation.scala:37-52
@@ -277,8 +310,20 @@ int64_t dq_spark_hash64(int32_t spark_type, const void* value, int64_t len) {
         case DQ_TYPE_FLOAT: return (int64_t)xxh_int(float_to_int_bits(*(const float*)value), SPARK_HLL_SEED);
         case DQ_TYPE_DOUBLE: return (int64_t)xxh_long(double_to_long_bits(*(const double*)value), SPARK_HLL_SEED);
         case DQ_TYPE_STRING: return (int64_t)xxh_bytes((const uint8_t*)value, len, SPARK_HLL_SEED);
+        case DQ_TYPE_DECIMAL128: {
+            uint64_t w[2];
+            memcpy(w, value, 16);
+            return (int64_t)dec128_spark_hash(w[0], w[1], SPARK_HLL_SEED);
+        }
         default: return 0;
     }
+}
+
+double dq_dec128_to_double(const void* value, int32_t scale) {
+    if (!value || scale < 0 || scale > 38) return NAN;
+    uint64_t w[2];
+    memcpy(w, value, 16);
+    return dec128_to_double(w[0], w[1], scale);
 }
 
 }  // extern "C"

@@ -222,6 +222,9 @@ int dq_scan_sharded(dq_ctx* ctx, const dq_column* const* shard_columns, const in
     ctx->err.clear();
     if (ctx->subs.empty())
         return dq_scan(ctx, shard_columns[0], ncols, shard_rows[0], ops, nops, preds, npreds, out, 0);
+    for (int c = 0; c < ncols; ++c)
+        if (shard_columns[0] && shard_columns[0][c].spark_type == DQ_TYPE_DECIMAL128)
+            return dq::ctx_fail(ctx, DQ_ERR_UNSUPPORTED, "DECIMAL128 columns need a single-device context");
     return multi_scan(ctx, shard_columns, shard_rows, ncols, ops, nops, preds, npreds, out);
 }
 

@@ -351,7 +351,15 @@ class DistributedAnalysisRunner:
                 results[a] = a.toFailureMetric(e)
             else:
                 passed.append(a)
-        from .analyzers import KLLSketch
+        from .analyzers import KLLSketch, analyzer_columns, reject_wide_decimals
+        # 128-bit decimal columns are read by single-process runs only: an analyzer naming one fails alone (every
+        # rank sees the same schema, so every rank drops the same analyzers)
+        for a in list(passed):
+            try:
+                reject_wide_decimals(shard, analyzer_columns(a), "a distributed run")
+            except UnsupportedOnDevice as e:
+                results[a] = a.toFailureMetric(e)
+                passed.remove(a)
         kll = [a for a in passed if isinstance(a, KLLSketch)]
         shareable = [a for a in passed if isinstance(a, ScanShareableAnalyzer) and not isinstance(a, KLLSketch)]
         if kll:

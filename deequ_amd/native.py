@@ -29,6 +29,8 @@ STATUS_NAMES = {0: "DQ_OK", -1: "DQ_ERR_INVALID_ARGUMENT", -2: "DQ_ERR_UNSUPPORT
 
 TYPE_BOOLEAN, TYPE_BYTE, TYPE_SHORT, TYPE_INT, TYPE_LONG, TYPE_FLOAT, TYPE_DOUBLE, TYPE_STRING, \
     TYPE_DATE, TYPE_TIMESTAMP, TYPE_DECIMAL = range(1, 12)
+TYPE_DECIMAL128 = 12  # 16-byte unscaled cells, precision 19..38 (DQ_TYPE_DECIMAL128)
+DEC128_TILE_ROWS = 1024  # rows one workgroup of the decimal128 scan takes per step (dq_internal.h kD128TileRows)
 
 COL_DEVICE = 0x1
 COL_OFFSETS64 = 0x2  # STRING: int64 offsets (dq_frequencies only)
@@ -59,7 +61,7 @@ HLL_NUM_WORDS = 52
 FREQ_PATHS = ("fast", "fast_narrow", "fast_done", "exact", "partitioned", "sorted", "small", "small_optimistic", "fast_spill",
               "split_buckets", "long_tuples")
 SCAN_KERNELS = ("striped", "striped_heavy", "heavy8", "heavy8_full", "bits", "pred_simple", "pred_vm", "regex",
-                "strings", "where_fused", "where_masks")
+                "strings", "where_fused", "where_masks", "decimal128")
 
 # Every symbol include/dq.h declares (checked by tests/test_native_abi.py).
 EXPORTED_SYMBOLS = (
@@ -72,7 +74,7 @@ EXPORTED_SYMBOLS = (
     "dq_scan_streamed", "dq_scan_kernel_launches", "dq_freq_path_count", "dq_kll_sketch_columns",
     "dq_kll_merge_states", "dq_scratch_trim", "dq_frequencies_parts", "dq_set_priority",
     "dq_schema_validate", "dq_schema_launch_count", "dq_gather_rows", "dq_parse_int32", "dq_parse_decimal",
-    "dq_parse_timestamp", "dq_split_rows", "dq_split_row_is_test",
+    "dq_parse_timestamp", "dq_split_rows", "dq_split_row_is_test", "dq_dec128_to_double",
 )
 
 
@@ -107,15 +109,45 @@ class _NumMatchesAndCount(ctypes.Structure):
 
 class _Mean(ctypes.Structure):
     _fields_ = [("sum", ctypes.c_double), ("count", ctypes.c_int64), ("isum", ctypes.c_int64), ("exact", ctypes.c_int32),
-                ("pad", ctypes.c_int32)]
+                ("pad", ctypes.c_int32), ("wsum", ctypes.c_uint64 * 3), ("wscale", ctypes.c_int32),
+                ("woverflow", ctypes.c_int32)]
 
 
 class _Dbl(ctypes.Structure):
-    _fields_ = [("value", ctypes.c_double), ("isum", ctypes.c_int64), ("exact", ctypes.c_int32), ("pad", ctypes.c_int32)]
+    _fields_ = [("value", ctypes.c_double), ("isum", ctypes.c_int64), ("exact", ctypes.c_int32), ("pad", ctypes.c_int32),
+                ("wsum", ctypes.c_uint64 * 3), ("wscale", ctypes.c_int32), ("woverflow", ctypes.c_int32)]
+
+
+def wide_sum_value(limbs):
+    """The exact 192-bit two's-complement sum of a DECIMAL128 Sum / Mean state (three little-endian limbs) as an int."""
+    v = int(limbs[0]) | (int(limbs[1]) << 64) | (int(limbs[2]) << 128)
+    return v - (1 << 192) if v >> 191 else v
+
+
+def wide_sum_limbs(v):
+    v &= (1 << 192) - 1
+    return [v & 0xFFFFFFFFFFFFFFFF, (v >> 64) & 0xFFFFFFFFFFFFFFFF, v >> 128]
 
 
 class _StdDev(ctypes.Structure):
-    _fields_ = [("n", ctypes.c_double), ("avg", ctypes.c_double), ("m2", ctypes.c_double)]
+    _fields_ = [("n", ctypes.c_double), ("avg", ctypes.c_double), ("m2", ctypes.c_double),
+                ("xs1", ctypes.c_uint64 * 6), ("xs2", ctypes.c_uint64 * 11), ("exact", ctypes.c_int32),
+                ("pad", ctypes.c_int32)]
+
+
+MOMENT_S1_UNIT, MOMENT_S2_UNIT = 180, 360  # xs1 counts 2^-180, xs2 counts 2^-360 (dq_dec128.h)
+
+
+def limbs_value(limbs):
+    """Little-endian 64-bit limbs of a two's-complement integer -> Python int."""
+    n = len(limbs)
+    v = sum(int(x) << (64 * i) for i, x in enumerate(limbs))
+    return v - (1 << (64 * n)) if v >> (64 * n - 1) else v
+
+
+def value_limbs(v, n):
+    v &= (1 << (64 * n)) - 1
+    return [(v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(n)]
 
 
 class _Corr(ctypes.Structure):
@@ -289,6 +321,7 @@ def load_library(path=None):
             "dq_split_rows": (c_int, [c_void_p, c_int64, c_int64, ctypes.c_uint64, ctypes.c_double, c_void_p, c_void_p,
                                       c_void_p, c_void_p]),
             "dq_split_row_is_test": (c_int, [c_int64, ctypes.c_uint64, ctypes.c_double]),
+            "dq_dec128_to_double": (ctypes.c_double, [c_void_p, ctypes.c_int32]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name)
@@ -346,9 +379,21 @@ def kll_merge_states(a, b):
         cap = int(n)
 
 
+def dec128_cell(unscaled):
+    """The 16-byte little-endian two's-complement cell of an unscaled value (a ctypes buffer)."""
+    return ctypes.create_string_buffer((int(unscaled) & ((1 << 128) - 1)).to_bytes(16, "little"), 16)
+
+
+def dec128_to_double(unscaled, scale):
+    """dq_dec128_to_double: Decimal.toDouble of one DECIMAL128 cell (host-side, C-ABI; the kernel's own code)."""
+    return float(load_library().dq_dec128_to_double(dec128_cell(unscaled), int(scale)))
+
+
 def spark_hash64(spark_type, value):
     """Spark XxHash64Function.hash(value, type, 42) as a signed 64-bit int (test hook)."""
     lib = load_library()
+    if spark_type == TYPE_DECIMAL128:  # value: the unscaled integer
+        return lib.dq_spark_hash64(spark_type, dec128_cell(value), 16)
     if spark_type == TYPE_STRING:
         b = value.encode("utf-8") if isinstance(value, str) else bytes(value)
         buf = ctypes.create_string_buffer(b, len(b))

@@ -73,20 +73,52 @@ def _long_add(a, b):
     return (ea + eb + (1 << 63)) % (1 << 64) - (1 << 63)
 
 
+WIDE_LIMIT = 10 ** 38  # Spark's widest decimal holds 38 digits
+
+
+def _wide_add(a, b):
+    """A DECIMAL128 column's Sum / Mean partials carry the exact unscaled total and its scale (`wide`), as _long_add's
+    states carry the Long: Spark aggregates in decimal and casts the final total once (A/Sum.scala:40), so the merge
+    adds the integers and converts again. None when either side has none (or the scales differ)."""
+    wa, wb = getattr(a, "wide", None), getattr(b, "wide", None)
+    if wa is None or wb is None or wa[1] != wb[1]:
+        return None
+    return (wa[0] + wb[0], wa[1])
+
+
+def _wide_double(wide):
+    """The double nearest to total * 10^-scale (int / int true division rounds correctly); NaN past 38 digits."""
+    total, scale = wide
+    return float("nan") if abs(total) >= WIDE_LIMIT else total / 10 ** scale
+
+
+def _wide_check(wide, what):
+    if wide is not None and abs(wide[0]) >= WIDE_LIMIT:
+        from .metrics import MetricCalculationRuntimeException
+        raise MetricCalculationRuntimeException(
+            "%s: decimal overflow, the exact total has %d digits and Spark's sum type holds at most 38"
+            % (what, len(str(abs(wide[0])))))
+
+
 class MeanState(DoubleValuedState):
     """A/Mean.scala:25-34."""
 
-    def __init__(self, sum_, count, exact=None):
+    def __init__(self, sum_, count, exact=None, wide=None):
         self.sum_, self.count = float(sum_), int(count)
         self.exact = exact  # the exact Long partial of an integral column (see _long_add), else None
+        self.wide = wide    # (exact unscaled total, scale) of a DECIMAL128 column (see _wide_add), else None
 
     def sum(self, other):
+        w = _wide_add(self, other)
+        if w is not None:
+            return MeanState(_wide_double(w), self.count + other.count, wide=w)
         e = _long_add(self, other)
         if e is not None:
             return MeanState(float(e), self.count + other.count, e)
         return MeanState(self.sum_ + other.sum_, self.count + other.count)
 
     def metricValue(self):
+        _wide_check(self.wide, "Mean")
         return float("nan") if self.count == 0 else self.sum_ / self.count
 
     def __eq__(self, o):
@@ -101,17 +133,22 @@ class MeanState(DoubleValuedState):
 class SumState(DoubleValuedState):
     """A/Sum.scala:25-33."""
 
-    def __init__(self, sum_, exact=None):
+    def __init__(self, sum_, exact=None, wide=None):
         self.sum_ = float(sum_)
         self.exact = exact
+        self.wide = wide
 
     def sum(self, other):
+        w = _wide_add(self, other)
+        if w is not None:
+            return SumState(_wide_double(w), wide=w)
         e = _long_add(self, other)
         if e is not None:
             return SumState(float(e), e)
         return SumState(self.sum_ + other.sum_)
 
     def metricValue(self):
+        _wide_check(self.wide, "Sum")
         return self.sum_
 
     def __eq__(self, o):
@@ -184,15 +221,27 @@ class MaxState(DoubleValuedState):
 class StandardDeviationState(DoubleValuedState):
     """A/StandardDeviation.scala:25-45 (Chan merge)."""
 
-    def __init__(self, n, avg, m2):
+    def __init__(self, n, avg, m2, sums=None):
         if not n > 0.0:
             raise ValueError("requirement failed: Standard deviation is undefined for n = 0.")
         self.n, self.avg, self.m2 = float(n), float(avg), float(m2)
+        # DECIMAL128 columns: the exact integer sums of x (units of 2^-180) and x^2 (2^-360) over the rows. With
+        # them avg and m2 are the exact moments rounded once, so any cut of the rows into partial states gives the
+        # same bits; states without them (other column types, loaded from a provider) merge as the reference does.
+        self.sums = sums
+        if sums is not None:
+            from fractions import Fraction
+            cnt, s1, s2 = int(self.n), sums[0], sums[1]
+            self.avg = float(Fraction(s1, cnt << N.MOMENT_S1_UNIT))
+            self.m2 = float(Fraction(cnt * s2 - s1 * s1, cnt << N.MOMENT_S2_UNIT))
 
     def metricValue(self):
         return math.sqrt(self.m2 / self.n)
 
     def sum(self, other):
+        if self.sums is not None and getattr(other, "sums", None) is not None:
+            return StandardDeviationState(self.n + other.n, 0.0, 0.0,
+                                          sums=(self.sums[0] + other.sums[0], self.sums[1] + other.sums[1]))
         newN = self.n + other.n
         delta = other.avg - self.avg
         deltaN = 0.0 if newN == 0.0 else delta / newN
@@ -421,8 +470,12 @@ def state_from_native(st):
     if k in (N.OP_COMPLETENESS, N.OP_COMPLIANCE):
         return NumMatchesAndCount(u.num_matches_and_count.num_matches, u.num_matches_and_count.count)
     if k == N.OP_MEAN:
+        if u.mean.exact == 2:
+            return MeanState(u.mean.sum, u.mean.count, wide=(N.wide_sum_value(u.mean.wsum), int(u.mean.wscale)))
         return MeanState(u.mean.sum, u.mean.count, u.mean.isum if u.mean.exact else None)
     if k == N.OP_SUM:
+        if u.dbl.exact == 2:
+            return SumState(u.dbl.value, wide=(N.wide_sum_value(u.dbl.wsum), int(u.dbl.wscale)))
         return SumState(u.dbl.value, u.dbl.isum if u.dbl.exact else None)
     if k in (N.OP_MINIMUM, N.OP_MIN_LENGTH):
         return MinState(u.dbl.value)
@@ -431,6 +484,9 @@ def state_from_native(st):
     if k == N.OP_STANDARD_DEVIATION:
         if u.stddev.n == 0.0:
             return None
+        if u.stddev.exact == 1:
+            return StandardDeviationState(u.stddev.n, u.stddev.avg, u.stddev.m2,
+                                          sums=(N.limbs_value(u.stddev.xs1), N.limbs_value(u.stddev.xs2)))
         return StandardDeviationState(u.stddev.n, u.stddev.avg, u.stddev.m2)
     if k == N.OP_CORRELATION:
         if not u.corr.n > 0.0:

@@ -21,6 +21,9 @@ SPARK_TYPE_NAMES = {
     N.TYPE_DOUBLE: "DoubleType", N.TYPE_STRING: "StringType", N.TYPE_DATE: "DateType",
     N.TYPE_TIMESTAMP: "TimestampType", N.TYPE_DECIMAL: "DecimalType",
 }
+WIDE_DECIMAL_NAME = "DecimalType"  # TYPE_DECIMAL128 shares Spark's type name: the precision tells them apart
+# One DECIMAL128 cell: the 16-byte little-endian two's-complement unscaled value, Arrow's decimal128 cell.
+DEC128_DTYPE = np.dtype([("lo", "<u8"), ("hi", "<i8")])
 _NAME_TO_TYPE = {v.lower().replace("type", ""): k for k, v in SPARK_TYPE_NAMES.items()}
 _NAME_TO_TYPE.update({"int": N.TYPE_INT, "bigint": N.TYPE_LONG, "bool": N.TYPE_BOOLEAN, "str": N.TYPE_STRING,
                       "float64": N.TYPE_DOUBLE, "float32": N.TYPE_FLOAT, "int64": N.TYPE_LONG,
@@ -28,9 +31,30 @@ _NAME_TO_TYPE.update({"int": N.TYPE_INT, "bigint": N.TYPE_LONG, "bool": N.TYPE_B
 
 NUMPY_OF = {N.TYPE_BOOLEAN: np.uint8, N.TYPE_BYTE: np.int8, N.TYPE_SHORT: np.int16, N.TYPE_INT: np.int32,
             N.TYPE_LONG: np.int64, N.TYPE_FLOAT: np.float32, N.TYPE_DOUBLE: np.float64, N.TYPE_DATE: np.int32,
-            N.TYPE_TIMESTAMP: np.int64, N.TYPE_DECIMAL: np.int64}
+            N.TYPE_TIMESTAMP: np.int64, N.TYPE_DECIMAL: np.int64, N.TYPE_DECIMAL128: DEC128_DTYPE}
 
-NUMERIC_TYPES = (N.TYPE_BYTE, N.TYPE_SHORT, N.TYPE_INT, N.TYPE_LONG, N.TYPE_FLOAT, N.TYPE_DOUBLE, N.TYPE_DECIMAL)
+NUMERIC_TYPES = (N.TYPE_BYTE, N.TYPE_SHORT, N.TYPE_INT, N.TYPE_LONG, N.TYPE_FLOAT, N.TYPE_DOUBLE, N.TYPE_DECIMAL,
+                 N.TYPE_DECIMAL128)
+_DECIMAL_PS = re.compile(r"^\s*decimal(?:type)?\s*\(\s*(\d+)\s*,\s*(\d+)\s*\)\s*$", re.I)
+
+
+def decimal_precision_scale(name):
+    """(precision, scale) of a type string with explicit "(p,s)", e.g. "decimal(38,18)"; None otherwise."""
+    m = _DECIMAL_PS.match(name) if isinstance(name, str) else None
+    return (int(m.group(1)), int(m.group(2))) if m else None
+
+
+def dec128_cells(unscaled):
+    """Python ints -> DEC128_DTYPE cells (two's complement); a value outside 128 bits raises OverflowError."""
+    out = np.zeros(len(unscaled), dtype=DEC128_DTYPE)
+    if len(unscaled):
+        out[:] = np.frombuffer(b"".join(int(v).to_bytes(16, "little", signed=True) for v in unscaled), dtype=DEC128_DTYPE)
+    return out
+
+
+def dec128_int(cell):
+    """One DEC128_DTYPE cell -> its unscaled Python int."""
+    return (int(cell["hi"]) << 64) | int(cell["lo"])
 
 
 def spark_type_of(name_or_code):
@@ -79,6 +103,8 @@ class Column:
 
     @property
     def type_name(self):
+        if self.spark_type == N.TYPE_DECIMAL128:
+            return "%s(%d,%d)" % (WIDE_DECIMAL_NAME, self.decimal_precision, self.decimal_scale)
         n = SPARK_TYPE_NAMES[self.spark_type]
         if self.spark_type == N.TYPE_DECIMAL:
             return "DecimalType(%d,%d)" % (self.decimal_precision, self.decimal_scale)
@@ -86,6 +112,9 @@ class Column:
 
     def is_numeric(self):
         return self.spark_type in NUMERIC_TYPES
+
+    def is_wide_decimal(self):
+        return self.spark_type == N.TYPE_DECIMAL128
 
     def null_mask(self):
         return ~unpack_validity(self.validity, self.length)
@@ -123,7 +152,7 @@ class Column:
         t = d["values"]
         dt = np.dtype(NUMPY_OF[self.spark_type])
         if str(t.dtype) == "torch.uint8" and dt.itemsize > 1:
-            v = t[i * dt.itemsize:(i + 1) * dt.itemsize].cpu().numpy().view(dt)[0]
+            v = t.reshape(-1)[i * dt.itemsize:(i + 1) * dt.itemsize].cpu().numpy().view(dt)[0]
         else:
             v = t[i:i + 1].cpu().numpy().astype(dt)[0]
         return self._decode_cell(v)
@@ -166,7 +195,7 @@ class Column:
         dt = np.dtype(NUMPY_OF[self.spark_type])
         if str(t.dtype) == "torch.uint8" and dt.itemsize > 1:
             pos = (idx[:, None] * dt.itemsize + torch.arange(dt.itemsize, device=dev)[None, :]).reshape(-1)
-            vals = t[pos].cpu().numpy().view(dt)
+            vals = t.reshape(-1)[pos].cpu().numpy().view(dt)
         else:
             vals = t[idx].cpu().numpy().astype(dt)
         return [self._decode_cell(v) if ok else None for v, ok in zip(vals, valid)]
@@ -178,6 +207,9 @@ class Column:
             return float(v)
         if self.spark_type == N.TYPE_DECIMAL:
             return int(v) / (10 ** self.decimal_scale)
+        if self.spark_type == N.TYPE_DECIMAL128:
+            from decimal import Context, Decimal
+            return Decimal(dec128_int(v)).scaleb(-self.decimal_scale, context=Context(prec=60))  # exact: <= 39 digits
         return int(v)
 
     def native(self):
@@ -251,7 +283,41 @@ class PartedColumn(Column):
         return out
 
 
+def _wide_column_from_pylist(name, precision, scale, items):
+    """decimal.Decimal / int / str cells -> a DECIMAL128 column of decimal(precision, scale); a cell that does not fit
+    (more fraction digits than the scale, or more than `precision` digits) raises ValueError."""
+    import decimal
+    if not (19 <= precision <= 38 and 0 <= scale <= precision):
+        raise ValueError("column %s: decimal(%d,%d) is not a wide decimal (19 <= p <= 38, 0 <= s <= p)"
+                         % (name, precision, scale))
+    unscaled, mask = [], []
+    with decimal.localcontext() as c:
+        c.prec = 100
+        for x in items:
+            mask.append(x is not None)
+            if x is None:
+                unscaled.append(0)
+                continue
+            if isinstance(x, float):
+                raise ValueError("column %s: a float cell (%r) is not an exact decimal; pass Decimal, int or str"
+                                 % (name, x))
+            try:
+                d = decimal.Decimal(x)
+            except decimal.InvalidOperation:
+                raise ValueError("column %s: %r is not a decimal" % (name, x))
+            u = d.scaleb(scale)
+            if not d.is_finite() or u != u.to_integral_value() or abs(int(u)) >= 10 ** precision:
+                raise ValueError("column %s: %r does not fit decimal(%d,%d)" % (name, x, precision, scale))
+            unscaled.append(int(u))
+    mask = np.array(mask, dtype=bool)
+    return Column(name, N.TYPE_DECIMAL128, dec128_cells(unscaled), None if mask.all() else pack_validity(mask),
+                  decimal_precision=precision, decimal_scale=scale)
+
+
 def _column_from_pylist(name, spark_type, items):
+    ps = decimal_precision_scale(spark_type)
+    if ps is not None and ps[0] > 18:
+        return _wide_column_from_pylist(name, ps[0], ps[1], items)
     t = spark_type_of(spark_type)
     n = len(items)
     mask = np.array([x is not None and not (isinstance(x, float) and math.isnan(x) and t == N.TYPE_STRING)
@@ -285,11 +351,11 @@ def _arrow_validity(arr, n):
     return pack_validity(mask)
 
 
-def _column_from_arrow(name, arr, pa):
+def _column_from_arrow(name, arr, pa, wide_decimals=False):
     t, n = arr.type, len(arr)
     validity = _arrow_validity(arr, n)
     if pa.types.is_dictionary(t):
-        return _column_from_arrow(name, arr.dictionary_decode(), pa)
+        return _column_from_arrow(name, arr.dictionary_decode(), pa, wide_decimals)
     if pa.types.is_large_string(t):
         arr, t = arr.cast(pa.string()), pa.string()
     if pa.types.is_string(t):
@@ -304,9 +370,17 @@ def _column_from_arrow(name, arr, pa):
         vals = np.unpackbits(bits, bitorder="little", count=arr.offset + n)[arr.offset:].astype(np.uint8)
         return Column(name, N.TYPE_BOOLEAN, vals, validity)
     if pa.types.is_decimal(t):
+        if t.precision > 18 and wide_decimals and pa.types.is_decimal128(t):
+            # the Arrow cells are the DECIMAL128 layout: taken as they are (NULL slots zeroed, as the int64 path does)
+            cells = np.frombuffer(arr.buffers()[1], dtype=DEC128_DTYPE)[arr.offset:arr.offset + n]
+            if validity is not None:
+                cells = cells.copy()
+                cells[~unpack_validity(validity, n)] = np.zeros((), dtype=DEC128_DTYPE)
+            return Column(name, N.TYPE_DECIMAL128, cells, validity, decimal_precision=t.precision,
+                          decimal_scale=t.scale)
         if t.precision > 18:
-            raise ValueError("column %s: DecimalType(%d,%d) exceeds the 64-bit unscaled range"
-                             % (name, t.precision, t.scale))
+            raise ValueError("column %s: DecimalType(%d,%d) exceeds the 64-bit unscaled range (wide_decimals=True "
+                             "loads it as a 128-bit decimal column)" % (name, t.precision, t.scale))
         # decimal128 cells are 16-byte little-endian two's complement; precision <= 18 fits the low 8 bytes
         cells = np.frombuffer(arr.buffers()[1], dtype=np.int64)[2 * arr.offset:2 * (arr.offset + n)]
         unscaled = np.ascontiguousarray(cells[0::2])
@@ -346,6 +420,10 @@ def column_to_arrow(col, pa):
         return pa.array(np.asarray(col.values, dtype=np.int32)[:n], type=pa.int32(), mask=mask).cast(pa.date32())
     if t == N.TYPE_TIMESTAMP:
         return pa.array(np.asarray(col.values, dtype=np.int64)[:n], type=pa.int64(), mask=mask).cast(pa.timestamp("us"))
+    if t == N.TYPE_DECIMAL128:
+        cells = np.ascontiguousarray(np.asarray(col.values, dtype=DEC128_DTYPE)[:n])
+        return pa.Array.from_buffers(pa.decimal128(col.decimal_precision, col.decimal_scale), n,
+                                     [vbuf, pa.py_buffer(cells.tobytes())], null_count=-1)
     if t == N.TYPE_DECIMAL:
         u = np.asarray(col.values, dtype=np.int64)[:n]
         cells = np.empty(2 * n, dtype=np.int64)
@@ -429,24 +507,26 @@ class Table:
         return cls(cols)
 
     @classmethod
-    def from_arrow(cls, table):
+    def from_arrow(cls, table, wide_decimals=False):
         """pyarrow.Table (a Spark DataFrame collected through Arrow, or a parquet read) -> Table.
         Fixed-width values and UTF-8 offsets/data are taken from the Arrow buffers without a
         per-row pass; validity bitmaps are realigned to bit 0 and padded; booleans are widened to one
         byte per row, timestamps normalised to Spark's microseconds, decimals (precision <= 18) to
-        unscaled longs."""
+        unscaled longs. decimal128(p > 18, s) columns raise unless `wide_decimals`: then they load as 128-bit
+        decimal columns (DQ_TYPE_DECIMAL128, the Arrow cells as they are), which the fused scan and the cast accept;
+        every other analyzer over such a column fails alone."""
         import pyarrow as pa
         cols = []
         for name, chunked in zip(table.column_names, table.columns):
             arr = chunked.combine_chunks() if chunked.num_chunks != 1 else chunked.chunk(0)
-            cols.append(_column_from_arrow(name, arr, pa))
+            cols.append(_column_from_arrow(name, arr, pa, wide_decimals))
         return cls(cols)
 
     @classmethod
-    def from_parquet(cls, path, columns=None):
+    def from_parquet(cls, path, columns=None, wide_decimals=False):
         """Parquet file or directory -> Table (through pyarrow, then `from_arrow`)."""
         import pyarrow.parquet as pq
-        return cls.from_arrow(pq.read_table(path, columns=columns))
+        return cls.from_arrow(pq.read_table(path, columns=columns), wide_decimals=wide_decimals)
 
     # ---- schema / access ------------------------------------------------------------------------
     @property
@@ -494,7 +574,7 @@ class Table:
                 d["values"] = torch.from_numpy(np.concatenate([c.values, np.zeros(16, np.uint8)])).to(dev)
                 d["offsets"] = torch.from_numpy(c.offsets.astype(np.int32)).to(dev)
             else:
-                d["values"] = torch.from_numpy(np.ascontiguousarray(c.values).view(np.uint8).copy()).to(dev)
+                d["values"] = torch.from_numpy(np.ascontiguousarray(c.values).view(np.uint8).reshape(-1).copy()).to(dev)
             if c.validity is not None:
                 d["validity"] = torch.from_numpy(pack_validity(unpack_validity(c.validity, c.length))).to(dev)
             c.device = d

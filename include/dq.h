@@ -63,7 +63,13 @@ typedef enum dq_spark_type {
     DQ_TYPE_STRING = 8,     /* UTF-8 bytes in `values`, int32 `offsets`  */
     DQ_TYPE_DATE = 9,       /* int32 days since epoch                    */
     DQ_TYPE_TIMESTAMP = 10, /* int64 microseconds since epoch            */
-    DQ_TYPE_DECIMAL = 11    /* int64 unscaled value, precision <= 18     */
+    DQ_TYPE_DECIMAL = 11,   /* int64 unscaled value, precision <= 18     */
+    /* 16-byte little-endian two's-complement unscaled value (Arrow's decimal128 cell), 19 <= decimal_precision <= 38,
+     * 0 <= decimal_scale <= precision; device values 16-byte aligned; results are defined for |unscaled| < 10^38.
+     * Spark hashes and stores precision <= 18 as longs: those stay DQ_TYPE_DECIMAL. Accepted by single-device dq_scan
+     * (Completeness, Sum, Mean, Minimum, Maximum, StandardDeviation, ApproxCountDistinct; a `where` may read other
+     * columns) and as a dq_cast_column source; every other entry point fails it with DQ_ERR_UNSUPPORTED. */
+    DQ_TYPE_DECIMAL128 = 12
 } dq_spark_type;
 
 #define DQ_COL_DEVICE 0x1u /* values/validity/offsets are device pointers on the ctx's GPU */
@@ -187,10 +193,21 @@ typedef struct dq_state {
         /* MeanState / SumState. For integral (non-decimal) columns Spark sums in a Long that wraps around and
          * casts the FINAL sum to Double (A/Sum.scala:34-37): `isum` keeps that exact Long partial and
          * `exact` = 1 so merges of shards / chunks (dq_state_merge, dq_state_fold) add the Longs and re-cast,
-         * rather than adding rounded doubles. `sum` / `value` is always (double)isum then. */
-        struct { double sum; int64_t count; int64_t isum; int32_t exact; int32_t pad; } mean;
-        struct { double value; int64_t isum; int32_t exact; int32_t pad; } dbl;  /* Sum/Min/Max State */
-        struct { double n, avg, m2; } stddev;                               /* StandardDeviationState */
+         * rather than adding rounded doubles. `sum` / `value` is always (double)isum then.
+         * DQ_TYPE_DECIMAL128 columns: `exact` = 2 and `wsum` is the exact 192-bit sum of the unscaled values (three
+         * little-endian 64-bit limbs, two's complement) with the column's scale in `wscale`; merges add the limbs and
+         * convert again (Spark aggregates in decimal and casts once, A/Sum.scala:40). `woverflow` = 1 when the total
+         * has 39 or more digits (|wsum| >= 10^38: Spark's sum type is at most decimal(38, s)); `sum` / `value` is NaN
+         * then and the host fails that analyzer alone. */
+        struct { double sum; int64_t count; int64_t isum; int32_t exact; int32_t pad;
+                 uint64_t wsum[3]; int32_t wscale; int32_t woverflow; } mean;
+        struct { double value; int64_t isum; int32_t exact; int32_t pad;
+                 uint64_t wsum[3]; int32_t wscale; int32_t woverflow; } dbl;  /* Sum/Min/Max State */
+        /* StandardDeviationState. DQ_TYPE_DECIMAL128 columns: `exact` = 1 and xs1 / xs2 are the exact sums of the
+         * per-row doubles x and of x^2 as two's-complement integers (little-endian 64-bit limbs) in units of 2^-180
+         * and 2^-360: merges add them, so any cut of the rows gives the same bits; avg / m2 are the fp64 Welford /
+         * Chan values of the same rows (within 1e-12 of the exact ones). */
+        struct { double n, avg, m2; uint64_t xs1[6]; uint64_t xs2[11]; int32_t exact; int32_t pad; } stddev;
         struct { double n, x_avg, y_avg, ck, x_mk, y_mk; } corr;            /* CorrelationState    */
         struct { int64_t words[DQ_HLL_NUM_WORDS]; } hll;                    /* ApproxCountDistinctState */
         struct { int64_t num_null, num_fractional, num_integral, num_boolean, num_string; } datatype;
@@ -306,7 +323,8 @@ typedef enum dq_scan_kernel {
     DQ_KERNEL_STRINGS = 8,        /* scan_strings_kernel                                                          */
     DQ_KERNEL_WHERE_FUSED = 9,    /* a value scan that also evaluates a `where` and writes its masks              */
     DQ_KERNEL_WHERE_MASKS = 10,   /* where_masks_kernel: a `where` into per-column masks (no fused producer)       */
-    DQ_KERNEL_COUNT = 11
+    DQ_KERNEL_DECIMAL128 = 11,    /* scan_decimal128_kernel: every (DECIMAL128 column, where) slot of a call      */
+    DQ_KERNEL_COUNT = 12
 } dq_scan_kernel;
 int64_t dq_scan_kernel_launches(const dq_ctx* ctx, int32_t kernel);
 
@@ -341,8 +359,13 @@ int dq_state_fold(const dq_state* states, int nparts, int nops, dq_state* out);
  * Java int-shift quirk `1 << Midx` and precision-9 bias correction; returns the rounded estimate. */
 double dq_hll_count(const int64_t words[DQ_HLL_NUM_WORDS]);
 
-/* Spark XxHash64Function.hash(value, type, 42) for one fixed-width value (test hook). */
+/* Spark XxHash64Function.hash(value, type, 42) for one fixed-width value (test hook). DQ_TYPE_DECIMAL128: `value`
+ * points to the 16-byte cell; the hash is XXH64 over unscaledValue().toByteArray (minimal big-endian bytes). */
 int64_t dq_spark_hash64(int32_t spark_type, const void* value, int64_t len);
+
+/* Decimal.toDouble of one DQ_TYPE_DECIMAL128 cell (16 bytes at `value`): the double nearest to unscaled * 10^-scale,
+ * ties to even, 0 <= scale <= 38. Host only; the same code as the scan kernel and the cast. */
+double dq_dec128_to_double(const void* value, int32_t scale);
 
 /* Build the (key -> count) table of the given key columns (computeFrequencies). */
 int dq_frequencies(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows,
@@ -468,7 +491,7 @@ int64_t dq_kll_merge_states(const uint8_t* a, int64_t na, const uint8_t* b, int6
  * DOUBLE. STRING sources: UTF8String.toLong (no trimming, optional sign, digits, optional '.' + digits truncated,
  * overflow NULL) / java.lang.Double.parseDouble (correctly rounded); strings that do not parse become NULL.
  * Numeric sources: integers sign-extend / convert, FLOAT/DOUBLE -> LONG as Java's (long) (NaN 0, saturating),
- * DECIMAL(p <= 18) -> Decimal.toLong (truncating) / Decimal.toDouble, BOOLEAN -> 0/1. values_dev receives nrows x 8 B,
+ * DECIMAL(p <= 18) and DECIMAL128 -> Decimal.toLong (truncating, low 64 bits) / Decimal.toDouble, BOOLEAN -> 0/1. values_dev receives nrows x 8 B,
  * validity_dev ceil(nrows / 64) x 8 B (LSB-first bitmap); both device memory, 8-B aligned. Returns DQ_OK, or
  * DQ_ERR_UNSUPPORTED when a string needs Double.parseDouble's arbitrary-precision path (hexadecimal literal, or
  * more than 19 significant digits on a rounding boundary) — never a silent guess. On a multi-device context
