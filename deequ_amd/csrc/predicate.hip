@@ -24,10 +24,10 @@ namespace {
 struct Val {
     int32_t tag;   // dq_value_tag
     int32_t null;
-    int64_t i;     // BOOL / LONG
+    int64_t i;     // BOOL / LONG; a DOUBLE loaded from a DECIMAL column: its unscaled long
     double d;      // DOUBLE
     const uint8_t* s;
-    int32_t slen;
+    int32_t slen;  // STRING; a DOUBLE loaded from a DECIMAL column: the column's scale
     int32_t xf;    // STRING read through lower() / upper(): 0 none, 1 lower, 2 upper (rx::case_map)
 };
 
@@ -260,9 +260,16 @@ __device__ Val load_col(const PredColumn& c, int64_t row) {
         case DQ_TYPE_LONG:
         case DQ_TYPE_TIMESTAMP: return vlong(static_cast<const int64_t*>(c.values)[row]);
         case DQ_TYPE_DECIMAL: {
-            double d = (double)static_cast<const int64_t*>(c.values)[row];
-            for (int k = 0; k < c.decimal_scale; ++k) d /= 10.0;
-            return vdouble(d);
+            // Spark's Decimal.toDouble of a compact decimal: one division by 10^scale (scale <= 18, so every
+            // product below is exact in fp64), as the scan and CAST read it. Dividing by 10 scale times rounds
+            // at every step and misses the literal's double (7 / 10 / 10 != 0.07).
+            const int64_t u = static_cast<const int64_t*>(c.values)[row];
+            double p = 1.0;
+            for (int k = 0; k < c.decimal_scale; ++k) p *= 10.0;
+            Val v = vdouble((double)u / p);
+            v.i = u;  // the digits, for Cast(decimal AS STRING) under RLIKE
+            v.slen = c.decimal_scale;
+            return v;
         }
         case DQ_TYPE_FLOAT: return vdouble((double)static_cast<const float*>(c.values)[row]);
         case DQ_TYPE_DOUBLE: return vdouble(static_cast<const double*>(c.values)[row]);
@@ -305,6 +312,7 @@ __device__ Val arith(int op, const Val& a, const Val& b, int32_t* status) {
         case DQ_P_MOD:
             if (integral) {
                 if (y.i == 0) return vnull();
+                if (y.i == -1) return vlong(0);  // Long.MinValue % -1 is 0 in Java, undefined in C++
                 return vlong(x.i % y.i);
             } else {
                 const double dy = as_double(y);
@@ -332,15 +340,19 @@ __device__ void spark_ymd(int64_t days, int64_t& y, int& m, int& d) {
 }
 
 // Spark's Cast(x AS STRING) of a non-string operand of RLIKE into buf (rx_engine.h formatters, java_dtoa.h).
-__device__ int value_string(const Val& v, int spark_type, int scale, uint8_t* buf) {
+// spark_type: the column type of a value that came straight from a column, else 0. A DECIMAL column's value prints as
+// BigDecimal.toString of its unscaled long at the column's scale ("1.50"), like PatternMatch's, not as its double.
+__device__ int value_string(const Val& v, int spark_type, uint8_t* buf) {
     if (v.tag == DQ_V_BOOL) {
         const char* t = v.i ? "true" : "false";
         const int n = v.i ? 4 : 5;
         for (int k = 0; k < n; ++k) buf[k] = (uint8_t)t[k];
         return n;
     }
-    if (v.tag == DQ_V_DOUBLE) return spark_type == DQ_TYPE_FLOAT ? java_float_to_chars((float)v.d, buf)
-                                                                 : java_double_to_chars(v.d, buf);
+    if (v.tag == DQ_V_DOUBLE) {
+        if (spark_type == DQ_TYPE_DECIMAL) return rx::format_decimal(v.i, v.slen, buf);
+        return spark_type == DQ_TYPE_FLOAT ? java_float_to_chars((float)v.d, buf) : java_double_to_chars(v.d, buf);
+    }
     if (spark_type == DQ_TYPE_DATE) return rx::format_date_days(v.i, buf);
     if (spark_type == DQ_TYPE_TIMESTAMP) return rx::format_timestamp_utc(v.i, buf);
     return rx::format_long(v.i, buf);
@@ -461,9 +473,14 @@ predicate_kernel(const PredProgram* __restrict__ progp, const PredColumn* __rest
                     const int n = arg;
                     const int base = sp - n;
                     Val r = vnull();
+                    int rt = 0;  // the column type travels with the operand taken (RLIKE prints by it)
                     for (int k = n - 1; k >= 0; --k)
-                        if (!st[base + k].null) r = st[base + k];
+                        if (!st[base + k].null) {
+                            r = st[base + k];
+                            rt = st_type[base + k];
+                        }
                     sp = base;
+                    st_type[sp] = rt;
                     st[sp++] = r;
                     break;
                 }
@@ -477,7 +494,7 @@ predicate_kernel(const PredProgram* __restrict__ progp, const PredColumn* __rest
                     Val a = st[sp - 1];
                     if (!a.null) {
                         if (a.tag == DQ_V_DOUBLE) a.d = -a.d;
-                        else a.i = -a.i;
+                        else a.i = (int64_t)(0ull - (uint64_t)a.i);  // Long.MinValue stays, as in Java
                         st[sp - 1] = a;
                     }
                     break;
@@ -505,7 +522,7 @@ predicate_kernel(const PredProgram* __restrict__ progp, const PredColumn* __rest
                         const uint8_t* sv = a.s;
                         int n = a.slen, xf = a.xf;
                         if (a.tag != DQ_V_STRING) {
-                            n = value_string(a, st_type[sp - 1], 0, buf);
+                            n = value_string(a, st_type[sp - 1], buf);
                             sv = buf;
                             xf = 0;
                         }

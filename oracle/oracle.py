@@ -826,8 +826,39 @@ class OracleParser:
         return PNode("col", value=val)
 
 # ---- predicate evaluation (3VL) ------------------------------------------------------------------
+# Values are Python objects: int = a Java long (every integral Spark type, promoted), float = a Java double, bool,
+# str, None = NULL. Where Python's numbers differ from Java's (unbounded ints, exact int / float comparison, fmod of
+# ints through floats) the helpers below restate Java's rule.
+class _DecimalCell(float):
+    """A DECIMAL(<= 18) cell: the double Spark's Decimal.toDouble gives for it (its value in every comparison and in
+    arithmetic, where it decays to a plain float), carrying the unscaled long and the scale for the one place that
+    reads the digits: Cast(decimal AS STRING) under RLIKE."""
+
+    def __new__(cls, unscaled, scale):
+        self = super().__new__(cls, float(unscaled) / 10.0 ** scale)
+        self.unscaled, self.scale = int(unscaled), int(scale)
+        return self
+
+
+def _wrap64(x):
+    """A Python int as the Java long the same arithmetic leaves: the low 64 bits, two's complement."""
+    return ((x + (1 << 63)) & ((1 << 64) - 1)) - (1 << 63)
+
+
+def _integral(v):
+    return isinstance(v, int)  # bool included: BOOLEAN takes part in arithmetic as 0 / 1
+
+
+def _java_rem(a, b):
+    """Java's long a % b for b != 0: truncated division, so the sign follows the dividend (Long.MIN % -1 = 0)."""
+    r = abs(a) % abs(b)
+    return -r if a < 0 else r
+
+
 def _cmp_vals(a, b):
-    """Spark comparison after PromoteStrings (string vs number -> double). None = NULL result."""
+    """Spark comparison after PromoteStrings (string vs number -> double) and the implicit cast of an integral
+    operand to double against a double one ((double) long: round to nearest, so 2^53 + 1 = 2^53 as doubles).
+    None = NULL result."""
     if isinstance(a, str) and isinstance(b, str):
         ab, bb = a.encode(), b.encode()
         return (ab > bb) - (ab < bb)
@@ -840,6 +871,8 @@ def _cmp_vals(a, b):
         a = int(a)
     if isinstance(b, bool):
         b = int(b)
+    if isinstance(a, float) != isinstance(b, float):  # long vs double: Python would compare the exact values
+        a, b = float(a), float(b)
     an = isinstance(a, float) and math.isnan(a)
     bn = isinstance(b, float) and math.isnan(b)
     if an or bn:
@@ -929,14 +962,21 @@ def _eval(node, row):
         op = node.value
         if op == "/":
             return None if b == 0 else float(a) / float(b)
-        if op == "%":
+        both = _integral(a) and _integral(b)
+        if op == "%":  # Spark's Remainder: NULL for a zero divisor; Java's % on longs, Math.fmod's rule on doubles
             if b == 0:
                 return None
-            return math.fmod(a, b) if isinstance(a, float) or isinstance(b, float) else int(math.fmod(a, b))
-        return {"+": a + b, "-": a - b, "*": a * b}[op]
+            if both:
+                return _java_rem(int(a), int(b))
+            a, b = float(a), float(b)  # Java's double %: fmod, NaN for an infinite dividend (math.fmod raises there)
+            return float("nan") if math.isinf(a) else math.fmod(a, b)
+        r = {"+": a + b, "-": a - b, "*": a * b}[op]
+        return _wrap64(r) if both else float(r)  # long arithmetic wraps to 64 bits
     if k == "neg":
         a = _eval(node.children[0], row)
-        return None if a is None else -a
+        if a is None:
+            return None
+        return _wrap64(-a) if _integral(a) else -a  # -Long.MIN = Long.MIN
     if k == "coalesce":
         for ch in node.children:
             v = _eval(ch, row)
@@ -977,7 +1017,10 @@ def _eval(node, row):
         a = _eval(node.children[0], row)
         if a is None:
             return None
-        text = a if isinstance(a, str) else ("true" if a is True else "false" if a is False else str(a))
+        if isinstance(a, _DecimalCell):  # Cast(decimal AS STRING) = BigDecimal.toString, not the double's text
+            text = java_bigdecimal_to_string(a.unscaled, a.scale)
+        else:
+            text = a if isinstance(a, str) else ("true" if a is True else "false" if a is False else str(a))
         return compile_java_regex(node.value).search(text) is not None
     if k in ("lower", "upper"):
         a = _eval(node.children[0], row)
@@ -1010,7 +1053,9 @@ def _eval(node, row):
         a = _eval(node.children[0], row)
         if isinstance(a, str):
             a = java_parse_double(a)
-        return None if a is None else abs(a)
+        if a is None:
+            return None
+        return _wrap64(abs(a)) if _integral(a) else abs(a)  # Math.abs(Long.MIN) = Long.MIN
     if k == "nanvl":
         a, b = _eval(node.children[0], row), _eval(node.children[1], row)
         if a is None or b is None:
@@ -1090,7 +1135,9 @@ def _valid(col):
 
 def _cell(col, i):
     """Row i's value as a Python object: UTF-8 text between offsets[i] and offsets[i + 1], or the fixed-width cell
-    read as its Spark type (BOOLEAN a byte, DECIMAL the unscaled long / 10^scale)."""
+    read as its Spark type (BOOLEAN a byte; DECIMAL Spark's Decimal.toDouble of a compact decimal, the unscaled long
+    as a double divided by the double 10^scale -- Python's int / int would round the exact quotient instead, another
+    double past 2^53)."""
     t = col.spark_type
     vals = _host_buffer(col, "values")
     if t == T_STRING:
@@ -1106,7 +1153,7 @@ def _cell(col, i):
     if t == T_DOUBLE:
         return float(np.frombuffer(raw, dtype="<f8")[0])
     x = int.from_bytes(raw, "little", signed=True)
-    return x / (10 ** col.decimal_scale) if t == T_DECIMAL else x
+    return _DecimalCell(x, col.decimal_scale) if t == T_DECIMAL else x
 
 
 _LE = {T_BYTE: "<i1", T_SHORT: "<i2", T_INT: "<i4", T_DATE: "<i4", T_FLOAT: "<f4", T_DOUBLE: "<f8"}
@@ -1132,7 +1179,7 @@ def _pylist(col):
         else:
             xs = np.frombuffer(raw, dtype=_LE.get(t, "<i8")).tolist()
             if t == T_DECIMAL:
-                xs = [x / (10 ** col.decimal_scale) for x in xs]
+                xs = [_DecimalCell(x, col.decimal_scale) for x in xs]
         cells = [x if valid[i] else None for i, x in enumerate(xs)]
     try:
         _CELLS[col] = cells

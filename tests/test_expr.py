@@ -187,3 +187,70 @@ def test_oracle_casts_follow_java_not_python():
             got = O._eval(O.OracleParser(text).parse(), row)
             assert got is exp or (got == exp and type(got) is type(exp)), (text, row, got, exp)
     assert math.isinf(O._eval(O.OracleParser("CAST(item AS DOUBLE)").parse(), {"item": "-Infinity"}))
+
+
+def test_oracle_numbers_follow_java_not_python():
+    """Numbers in the oracle are Java's, where Python's differ: long + - *, unary minus and abs wrap to 64 bits; % on
+    longs is Java's remainder in integer arithmetic (sign of the dividend, exact past 2^53, NULL for a zero divisor)
+    and stays fmod with a double operand; a long against a double is cast to double first (round to nearest even),
+    in comparisons, IN and <=>; a DECIMAL cell is Decimal.toDouble, (double) unscaled / 10.0^scale. Every expected
+    value below is worked out by hand from those rules, none is taken from the oracle."""
+    import numpy as np
+    import oracle as O
+    from deequ_amd.table import Column
+    big, small = (1 << 63) - 1, -(1 << 63)
+    p53 = 1 << 53  # 9007199254740992: from here on only even longs are doubles
+    cases = [
+        # + - * wrap: Long.MAX + 1 = Long.MIN, Long.MIN - 1 = Long.MAX, Long.MAX * 2 = -2, Long.MIN * -1 = Long.MIN
+        ({"att1": big}, {"att1 + 1": small, "att1 * 2": -2, "att1 + 1 < att1": True, "att1 + att1": -2}),
+        ({"att1": small}, {"att1 - 1": big, "att1 * -1": small, "-att1": small, "abs(att1)": small,
+                           "att1 % -1": 0, "-att1 < 0": True}),
+        ({"att1": -5}, {"-att1": 5, "abs(att1)": 5, "abs(att1 - 5)": 10}),
+        # Java's %: truncated division, the sign follows the dividend; NULL for x % 0
+        ({"att1": -7}, {"att1 % 3": -1, "att1 % -3": -1, "att1 % 0": None, "att1 % 7": 0,
+                        "att1 % 2.0": -1.0, "att1 % 0.0": None, "att1 % 2.5": -2.0}),
+        ({"att1": 7}, {"att1 % -3": 1, "att1 % 3": 1, "att1 % 0": None, "att1 % -2.0": 1.0}),
+        # in integer arithmetic: 2^53 + 1 is odd, and ends in ...993 (as doubles it would be 2^53: even, ...992)
+        ({"att1": p53 + 1}, {"att1 % 2": 1, "att1 % 10": 3, "-att1 % 2": -1}),
+        ({"att1": big}, {"att1 % 10": 7, "att1 % 2": 1}),
+        ({"att1": 7.5}, {"att1 % 2": 1.5, "-att1 % 2": -1.5}),
+        # Java's double %: an infinite dividend gives NaN (Python's math.fmod raises), an infinite divisor the dividend
+        ({"att1": float("inf"), "att2": 7.5}, {"isnan(att1 % 2)": True, "isnan(-att1 % 2.5)": True,
+                                               "att2 % att1": 7.5, "att1 % 0": None}),
+        # long vs double: the long becomes a double first; (double)(2^53 + 1) = 2^53 (the tie goes to the even
+        # mantissa), (double)(2^53 - 1) is exact
+        ({"att1": p53 + 1, "att2": float(p53)},
+         {"att1 = att2": True, "att2 = att1": True, "att1 > att2": False, "att2 < att1": False, "att1 <= att2": True,
+          "att2 >= att1": True, "att1 != att2": False, "att1 <=> att2": True, "att2 <=> att1": True,
+          "att1 IN (att2)": True, "att2 IN (att1)": True, "att1 IN (1.0, 2.0)": False,
+          "att1 = 9007199254740992.0": True, "9007199254740992.0 = att1": True, "att1 < 9007199254740994.0": True}),
+        ({"att1": p53 - 1, "att2": float(p53)},
+         {"att1 = att2": False, "att2 = att1": False, "att1 < att2": True, "att2 > att1": True,
+          "att1 <=> att2": False, "att1 IN (att2)": False, "att1 = 9007199254740991.0": True}),
+        ({"att1": -(p53 + 1), "att2": -float(p53)}, {"att1 = att2": True, "att2 = att1": True, "att1 < att2": False}),
+        # long vs long stays exact
+        ({"att1": p53 + 1, "att2": p53}, {"att1 = att2": False, "att1 > att2": True, "att1 <=> att2": False,
+                                          "att1 IN (att2)": False, "att1 - att2": 1}),
+    ]
+    for row, want in cases:
+        row = dict({"item": None, "att1": None, "att2": None}, **row)
+        for text, exp in want.items():
+            got = O._eval(O.OracleParser(text).parse(), row)
+            assert got is exp or (got == exp and type(got) is type(exp)), (text, row, got, exp)
+    # DECIMAL cells: 7 / 100.0 = 0.07 and -14 / 100.0 = -0.14 (one correctly rounded division: the literal's double);
+    # past 2^53, (double) 9007199254740995 = 9007199254740996.0 (tie to the even mantissa) and / 10.0 =
+    # 900719925474099.6 -> 900719925474099.625 (doubles there are 0.125 apart), where the exact quotient
+    # 900719925474099.5 is a double itself: Spark gives the former
+    col = Column("x", N.TYPE_DECIMAL, np.array([7, -14, 1999, 0], dtype=np.int64), decimal_precision=18, decimal_scale=2)
+    wide = Column("y", N.TYPE_DECIMAL, np.array([p53 + 3, -(p53 + 3)], dtype=np.int64), decimal_precision=18,
+                  decimal_scale=1)
+    for cells in ([O._cell(col, i) for i in range(4)], O._pylist(col)):
+        assert [float(c) for c in cells] == [0.07, -0.14, 19.99, 0.0]
+        assert all(isinstance(c, float) for c in cells)
+    for cells in ([O._cell(wide, i) for i in range(2)], O._pylist(wide)):
+        assert [float(c) for c in cells] == [900719925474099.625, -900719925474099.625]
+    row = {"x": O._pylist(col)[0], "att1": 7}
+    for text, exp in {"x = 0.07": True, "x <= 0.07": True, "x IN (0.07)": True, "x * 100 = att1": False,
+                      "x RLIKE '^0[.]07$'": True, "x RLIKE '^0[.]07$' AND x * 100 > 7": True}.items():
+        got = O._eval(O.OracleParser(text).parse(), row)
+        assert got is exp, (text, got, exp)
