@@ -876,10 +876,44 @@ def _block_from_dict(freq, like):
     return G.GroupBlock(cols, np.array([freq[k] for k in keys], dtype=np.int64))
 
 
+def dictionary_frequencies(data, column, include_nulls=False):
+    """The frequency table of one dictionary-encoded column kept on the device (table.DictColumn, or the chunks of a
+    ChunkedTable each with its own dictionary), or None when the column is anything else: the per-entry row counts
+    (dq_dict_counts, a 4-byte index histogram per chunk), the entries with a count > 0 of every chunk as one small
+    host column, and the existing weighted build over them (dq_frequencies_ex), where duplicate entries add up. The
+    NULL rows become one NULL entry for Histogram's NullValue group. The table is a weighted build like any merged
+    state's: it persists, loads and sums as the table of the decoded column does."""
+    from .table import DictColumn, PartedColumn, Table, _column_from_pylist
+    col = data[column]
+    parts = col.parts if isinstance(col, PartedColumn) else [col]
+    ctx = engine.ctx()
+    if getattr(ctx, "multi", False) or not all(isinstance(p, DictColumn) and p.dict_device is not None for p in parts):
+        return None
+    import torch
+    items, weights, nulls = [], [], 0
+    for p in parts:
+        nd = p.n_dict
+        counts = torch.empty(max(nd, 1), dtype=torch.int64, device=p.dict_device["indices"].device)
+        rows, nonnull = ctx.dict_counts(p.native_dict(), counts.data_ptr())
+        c = counts[:nd].cpu().numpy()
+        keep = np.flatnonzero(c > 0)
+        items.extend(p.dictionary.value_at(int(e)) for e in keep)  # a counted entry is never a NULL one
+        weights.extend(c[keep].tolist())
+        nulls += rows - nonnull
+    if include_nulls and nulls:
+        items.append(None)
+        weights.append(nulls)
+    entries_table = Table([_column_from_pylist(column, N.TYPE_STRING, items)])
+    return engine.frequencies(entries_table, [column], include_nulls=include_nulls,
+                              weights=np.asarray(weights, dtype=np.int64))
+
+
 def computeFrequencies(data, groupingColumns, include_nulls=False):
     """FrequencyBasedAnalyzer.computeFrequencies (A/GroupingAnalyzers.scala:53-79) on the GPU."""
     reject_wide_decimals(data, groupingColumns, "a grouping")
-    table = engine.frequencies(data, list(groupingColumns), include_nulls=include_nulls)
+    table = dictionary_frequencies(data, groupingColumns[0], include_nulls) if len(groupingColumns) == 1 else None
+    if table is None:
+        table = engine.frequencies(data, list(groupingColumns), include_nulls=include_nulls)
     return FrequenciesAndNumRows(table, table.num_rows, list(groupingColumns))
 
 
@@ -1062,7 +1096,9 @@ class Histogram(Analyzer):
         reject_wide_decimals(data, [self.column], "Histogram")
         if self.binningUdf is not None:
             return FrequenciesAndNumRows(self.binned_counts(data), data.count(), [self.column])
-        table = engine.frequencies(data, [self.column], include_nulls=True)
+        table = dictionary_frequencies(data, self.column, include_nulls=True)
+        if table is None:
+            table = engine.frequencies(data, [self.column], include_nulls=True)
         return FrequenciesAndNumRows(table, data.count(), [self.column])
 
     def binned_counts(self, data):
@@ -1071,7 +1107,9 @@ class Histogram(Analyzer):
         counted on the GPU, the UDF runs once per DISTINCT value (and once for NULL, as a Scala UDF over an object
         type sees the nulls), and the bins add the groups' counts — exact for any deterministic UDF. The UDF receives
         the column's value (str, int, float, ...), as a Spark UDF receives the Scala value. {(bin label,): count}."""
-        ft = engine.frequencies(data, [self.column], include_nulls=False)
+        ft = dictionary_frequencies(data, self.column, include_nulls=False)
+        if ft is None:
+            ft = engine.frequencies(data, [self.column], include_nulls=False)
         col = data[self.column] if self.udfInputAsString else None
         return self.bin_groups(((k[0], c) for k, c in ft.to_dict().items()), data.count() - ft.num_rows, col)
 

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "dq_common.h"
+#include "dq_dict.h"
 #include "dq_internal.h"
 #include "rx_engine.h"
 
@@ -1786,6 +1787,397 @@ int dq_synth_validity(dq_ctx* ctx, uint64_t seed, int64_t row0, int64_t nrows, i
     DQ_HIP(ctx, hipSetDevice(ctx->device));
     launch_synth_validity(seed, row0, nrows, null_permille, validity_dev, ctx->stream);
     DQ_HIP(ctx, hipGetLastError());
+    return DQ_OK;
+}
+
+}  // extern "C"
+
+// ---- dictionary-encoded STRING columns (dict.hip) ---------------------------------------------------------------------
+namespace {
+
+// DQ_DICT_LDS_ENTRIES=n (read per call): dictionaries of up to n entries count in LDS (at most kDictLdsWords).
+int dict_lds_entries() {
+    const char* e = getenv("DQ_DICT_LDS_ENTRIES");
+    const long v = e ? atol(e) : (long)kDictLdsWords;
+    return (int)std::max<long>(0, std::min<long>(v, kDictLdsWords));
+}
+
+// LDS counter copies of a slot, 0 = global atomics. A workgroup reads at most nrows / grid + 2 tiles of rows, which
+// must stay below 2^31 so that no 32-bit LDS counter can wrap.
+int dict_lds_copies(int n_dict, int64_t nrows, int grid) {
+    if (n_dict <= 0 || n_dict > dict_lds_entries()) return 0;
+    if (nrows / grid + 2 * kDictTileRows >= ((int64_t)1 << 31)) return 0;
+    int c = kDictLdsCopies;
+    if (const char* e = getenv("DQ_DICT_LDS_COPIES")) {  // 1, 2, 4 or 8: fewer copies (measurements)
+        const int v = atoi(e);
+        if (v == 1 || v == 2 || v == 4) c = v;
+    }
+    while (c > 1 && (int64_t)c * n_dict > kDictLdsCopyWords) c >>= 1;
+    return c;
+}
+
+int check_dict_column(dq_ctx* ctx, const dq_dict_column& d, int64_t nrows, int which) {
+    const dq_column& e = d.dictionary;
+    if (!(d.flags & DQ_COL_DEVICE) || !(e.flags & DQ_COL_DEVICE) || (e.flags & DQ_COL_OFFSETS64))
+        return fail(ctx, DQ_ERR_UNSUPPORTED, "dictionary column %d: device buffers with int32 offsets only", which);
+    if (d.length != nrows || nrows < 0 || (nrows > 0 && !d.indices))
+        return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dictionary column %d has %lld rows, batch has %lld", which,
+                    (long long)d.length, (long long)nrows);
+    if (e.spark_type != DQ_TYPE_STRING || e.length < 1 || e.length > INT32_MAX - 1 || !e.offsets || !e.validity || !e.values)
+        return fail(ctx, DQ_ERR_INVALID_ARGUMENT,
+                    "dictionary column %d: the dictionary is a STRING column of n_dict + 1 entries (the last one NULL) "
+                    "with offsets, a validity bitmap and bytes", which);
+    if (((uintptr_t)d.indices & 3) || ((uintptr_t)d.validity & 7) || ((uintptr_t)e.values & 3) ||
+        ((uintptr_t)e.offsets & 3) || ((uintptr_t)e.validity & 7))
+        return fail(ctx, DQ_ERR_ALIGNMENT, "dictionary column %d: misaligned buffer", which);
+    return DQ_OK;
+}
+
+// Pinned staging of one call's uploads (the buffer is free: the caller synchronised the stream).
+struct Stager {
+    dq_ctx* ctx;
+    Bump hb;
+    int upload(void* dst, const void* src, size_t n) {
+        if (!n) return DQ_OK;
+        void* h = hb.take(n, 16);
+        memcpy(h, src, n);
+        DQ_HIP(ctx, hipMemcpyAsync(dst, h, n, hipMemcpyHostToDevice, ctx->stream));
+        return DQ_OK;
+    }
+};
+
+size_t pred_stage_bytes(const dq_predicate& pr) {
+    return sizeof(PredProgram) + sizeof(int32_t) * (size_t)pr.code_len + sizeof(dq_const) * (size_t)std::max(pr.n_consts, 1) +
+           (size_t)std::max<int64_t>(pr.strings_len, 1) + 1024;
+}
+
+// One predicate over `columns` (pcols_dev: their PredColumn records on the device, pc: the same on the host) into TRUE /
+// NOT-NULL bitmaps of `pwords` words, by the kernels dq_scan evaluates predicates with. *status (device, zeroed) is
+// set by a row the device cannot evaluate (regex backtracking budget, inexact string -> double).
+int eval_predicate_bits(dq_ctx* ctx, const dq_predicate& pr, const dq_column* columns, int ncols, const PredColumn* pc,
+                        const PredColumn* pcols_dev, int64_t nrows, int64_t pwords, uint64_t* pt, uint64_t* pn,
+                        int32_t* status, ScratchBuffers& buf, Stager& up) {
+    if (pr.code_len < 2 || (pr.code_len & 1) || !pr.code) return fail(ctx, DQ_ERR_PREDICATE, "empty predicate program");
+    for (int k = 0; k + 1 < pr.code_len; k += 2) {
+        const int a = pr.code[k + 1];
+        if (pr.code[k] == DQ_P_COL && (a < 0 || a >= ncols))
+            return fail(ctx, DQ_ERR_PREDICATE, "predicate reads column %d of %d", a, ncols);
+        if ((pr.code[k] == DQ_P_CONST || pr.code[k] == DQ_P_REGEX || pr.code[k] == DQ_P_RLIKE || pr.code[k] == DQ_P_LIKE) &&
+            (a < 0 || a >= pr.n_consts))
+            return fail(ctx, DQ_ERR_PREDICATE, "predicate reads constant %d of %d", a, pr.n_consts);
+    }
+    void *dcode = nullptr, *dconst = nullptr, *dstr = nullptr, *dprog = nullptr;
+    DQ_HIP(ctx, buf.alloc(&dcode, sizeof(int32_t) * (size_t)pr.code_len));
+    DQ_HIP(ctx, buf.alloc(&dconst, sizeof(dq_const) * (size_t)std::max(pr.n_consts, 1)));
+    DQ_HIP(ctx, buf.alloc(&dstr, (size_t)std::max<int64_t>(pr.strings_len, 1) + 16));
+    DQ_HIP(ctx, buf.alloc(&dprog, sizeof(PredProgram)));
+    int rc = up.upload(dcode, pr.code, sizeof(int32_t) * (size_t)pr.code_len);
+    if (rc) return rc;
+    if (pr.n_consts > 0 && (rc = up.upload(dconst, pr.consts, sizeof(dq_const) * (size_t)pr.n_consts))) return rc;
+    if (pr.strings_len > 0 && (rc = up.upload(dstr, pr.strings, (size_t)pr.strings_len))) return rc;
+    PredProgram pg;
+    pg.code = (const int32_t*)dcode;
+    pg.consts = (const dq_const*)dconst;
+    pg.strings = (const uint8_t*)dstr;
+    pg.code_len = pr.code_len;
+    pg.n_consts = pr.n_consts;
+    if ((rc = up.upload(dprog, &pg, sizeof(pg)))) return rc;
+    if (pr.code_len == 4 && pr.code[0] == DQ_P_COL && pr.code[2] == DQ_P_REGEX) {
+        const dq_const& k = pr.consts[pr.code[3]];
+        launch_regex(pc[pr.code[1]], (const int32_t*)((const uint8_t*)dstr + k.str_offset), nrows, pwords, pt, pn, status,
+                     ctx->stream);
+        ctx->kernel_launches[DQ_KERNEL_REGEX]++;
+    } else if (PredSimple ps; !pred_vm_forced() && compile_simple_predicate(pr, columns, ncols, ps)) {
+        launch_pred_simple(ps, pcols_dev, nrows, pwords, pt, pn, ctx->stream);
+        ctx->kernel_launches[DQ_KERNEL_PRED_SIMPLE]++;
+    } else {
+        bool rx = false;
+        for (int k = 0; k + 1 < pr.code_len; k += 2) rx |= pr.code[k] == DQ_P_RLIKE;
+        launch_predicate((const PredProgram*)dprog, rx, status, pcols_dev, nrows, pwords, pt, pn, ctx->stream);
+        ctx->kernel_launches[DQ_KERNEL_PRED_VM]++;
+    }
+    DQ_HIP(ctx, hipGetLastError());
+    return DQ_OK;
+}
+
+void fill_dict_slot(DictSlot& s, const dq_dict_column& d) {
+    memset(&s, 0, sizeof(s));
+    s.indices = d.indices;
+    s.validity = (const uint64_t*)d.validity;
+    s.dict_data = (const uint8_t*)d.dictionary.values;
+    s.dict_offsets = d.dictionary.offsets;
+    s.n_dict = (int32_t)(d.dictionary.length - 1);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dq_dict_counts(dq_ctx* ctx, const dq_dict_column* dict, int64_t* counts_dev, int64_t* rows) {
+    if (!ctx || !dict || !rows) return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_dict_counts: invalid arguments");
+    ctx->err.clear();
+    if (!ctx->subs.empty()) return fail(ctx, DQ_ERR_UNSUPPORTED, "dq_dict_counts takes a single-device context");
+    const int64_t nrows = dict->length;
+    int rc = check_dict_column(ctx, *dict, nrows, 0);
+    if (rc) return rc;
+    DictSlot s;
+    fill_dict_slot(s, *dict);
+    if ((s.n_dict > 0 && !counts_dev) || ((uintptr_t)counts_dev & 7))
+        return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_dict_counts: counts_dev holds n_dict 8-byte aligned counts");
+    DQ_HIP(ctx, hipSetDevice(ctx->device));
+    ScratchBuffers buf(ctx);
+    int64_t* stats = nullptr;
+    DictSlot* dslot = nullptr;
+    DQ_HIP(ctx, buf.alloc((void**)&stats, sizeof(int64_t) * DS_COUNT));
+    DQ_HIP(ctx, buf.alloc((void**)&dslot, sizeof(DictSlot)));
+    const int grid = dict_counts_grid(ctx->cus, nrows);
+    s.counts = counts_dev;
+    s.stats = stats;
+    s.lds_copies = dict_lds_copies(s.n_dict, nrows, grid);
+    DQ_HIP(ctx, hipMemsetAsync(stats, 0, sizeof(int64_t) * DS_COUNT, ctx->stream));
+    if (s.n_dict > 0) DQ_HIP(ctx, hipMemsetAsync(counts_dev, 0, sizeof(int64_t) * (size_t)s.n_dict, ctx->stream));
+    DQ_HIP(ctx, hipMemcpyAsync(dslot, &s, sizeof(s), hipMemcpyHostToDevice, ctx->stream));
+    launch_dict_counts(dslot, 1, nrows, grid, s.lds_copies * s.n_dict, ctx->stream);
+    DQ_HIP(ctx, hipGetLastError());
+    ctx->kernel_launches[DQ_KERNEL_DICT_COUNTS]++;
+    int64_t h[DS_COUNT];
+    DQ_HIP(ctx, hipMemcpyAsync(h, stats, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (h[DS_BAD_INDEX])
+        return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_dict_counts: %lld non-NULL rows hold an index outside [0, %d)",
+                    (long long)h[DS_BAD_INDEX], s.n_dict);
+    rows[0] = nrows;
+    rows[1] = h[DS_NONNULL];
+    return DQ_OK;
+}
+
+int dq_dict_scan(dq_ctx* ctx, const dq_column* columns, int ncols, const dq_dict_column* dicts, int ndicts, int64_t nrows,
+                 const dq_op* ops, int nops, const dq_predicate* preds, int npreds, dq_state* out) {
+    if (!ctx) return DQ_ERR_INVALID_ARGUMENT;
+    ctx->err.clear();
+    if (nops < 0 || ncols < 0 || ndicts < 0 || npreds < 0 || nrows < 0 || (nops > 0 && (!ops || !out || !dicts)) ||
+        (ncols > 0 && !columns) || (npreds > 0 && !preds))
+        return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_dict_scan: invalid arguments");
+    if (nops == 0) return DQ_OK;
+    if (!ctx->subs.empty()) return fail(ctx, DQ_ERR_UNSUPPORTED, "dq_dict_scan takes a single-device context");
+    for (int d = 0; d < ndicts; ++d) {
+        const int rc = check_dict_column(ctx, dicts[d], nrows, d);
+        if (rc) return rc;
+    }
+    // ---- plan: one slot per (dictionary column, where); one predicate op per Compliance -------------------------
+    std::map<std::pair<int, int>, int> slot_of;
+    std::vector<DictSlot> slots;
+    std::vector<int> slot_dict, slot_where;
+    std::vector<DictOpMap> opmap(nops);
+    std::vector<int> pop_pred, pop_slot, op_pop(nops, -1);
+    std::vector<char> where_used(std::max(npreds, 1), 0);
+    for (int i = 0; i < nops; ++i) {
+        const dq_op& op = ops[i];
+        const int d = op.column[0] - ncols;
+        if (d < 0 || d >= ndicts) return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "op %d: column %d names no dictionary column", i, op.column[0]);
+        if (op.where < -1 || op.where >= npreds) return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "op %d: bad where index", i);
+        uint32_t flag = 0;
+        switch (op.kind) {
+            case DQ_OP_COMPLETENESS: break;
+            case DQ_OP_MIN_LENGTH: case DQ_OP_MAX_LENGTH: flag = SF_LEN; break;
+            case DQ_OP_DATATYPE: flag = SF_DTYPE; break;
+            case DQ_OP_APPROX_COUNT_DISTINCT: flag = SF_HLL; break;
+            case DQ_OP_COMPLIANCE:
+                if (op.predicate < 0 || op.predicate >= npreds)
+                    return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "op %d: Compliance needs a predicate", i);
+                break;
+            default:
+                return fail(ctx, DQ_ERR_UNSUPPORTED, "op %d: kind %d is not answered from a dictionary column", i, op.kind);
+        }
+        if (op.where >= 0) {
+            where_used[op.where] = 1;
+            const dq_predicate& w = preds[op.where];
+            for (int k = 0; k + 1 < w.code_len; k += 2)
+                if (w.code[k] == DQ_P_COL && (w.code[k + 1] < 0 || w.code[k + 1] >= ncols))
+                    return fail(ctx, DQ_ERR_UNSUPPORTED, "op %d: its where reads a dictionary column", i);
+        }
+        const auto key = std::make_pair(d, (int)op.where);
+        auto it = slot_of.find(key);
+        if (it == slot_of.end()) {
+            DictSlot s;
+            fill_dict_slot(s, dicts[d]);
+            it = slot_of.emplace(key, (int)slots.size()).first;
+            slots.push_back(s);
+            slot_dict.push_back(d);
+            slot_where.push_back(op.where);
+        }
+        slots[it->second].flags |= flag;
+        opmap[i].op = i;
+        opmap[i].kind = op.kind;
+        opmap[i].slot = it->second;
+        opmap[i].has_where = op.where >= 0;
+        opmap[i].sums = nullptr;
+        if (op.kind == DQ_OP_COMPLIANCE) {
+            op_pop[i] = (int)pop_pred.size();
+            pop_pred.push_back(op.predicate);
+            pop_slot.push_back(it->second);
+        }
+    }
+    const int nslots = (int)slots.size(), npops = (int)pop_pred.size();
+    if (nslots > kMaxSlots) return fail(ctx, DQ_ERR_UNSUPPORTED, "dq_dict_scan: more than %d slots", kMaxSlots);
+    for (int c = 0; c < ncols; ++c) {  // the plain columns a where reads
+        bool used = false;
+        for (int p = 0; p < npreds && !used; ++p)
+            for (int k = 0; where_used[p] && k + 1 < preds[p].code_len; k += 2)
+                used |= preds[p].code[k] == DQ_P_COL && preds[p].code[k + 1] == c;
+        if (!used) continue;
+        if (!(columns[c].flags & DQ_COL_DEVICE) || (columns[c].flags & DQ_COL_OFFSETS64) || columns[c].length != nrows ||
+            columns[c].spark_type == DQ_TYPE_DECIMAL128)
+            return fail(ctx, DQ_ERR_UNSUPPORTED, "dq_dict_scan: column %d of a where must be a device column of the batch's rows", c);
+    }
+    DQ_HIP(ctx, hipSetDevice(ctx->device));
+    const int grid = dict_counts_grid(ctx->cus, nrows);
+    // ---- device buffers --------------------------------------------------------------------------------------
+    ScratchBuffers buf(ctx);
+    size_t zwords = 0;  // one zeroed block: per slot stats, fold, counts, then the predicate ops' sums
+    std::vector<size_t> zoff(nslots);
+    int max_entries = 0;
+    for (int s = 0; s < nslots; ++s) {
+        zoff[s] = zwords;
+        zwords += DS_COUNT + DF_COUNT + (size_t)slots[s].n_dict + kHllRegs / 2;
+        max_entries = std::max(max_entries, slots[s].n_dict);
+    }
+    const size_t sums_off = zwords;
+    zwords += 2 * (size_t)std::max(npops, 1);
+    int64_t* zero = nullptr;
+    DQ_HIP(ctx, buf.alloc((void**)&zero, zwords * 8));
+    DictSlot* dslots = nullptr;
+    DictPredOp* dpops = nullptr;
+    DictOpMap* dops = nullptr;
+    dq_state* dout = nullptr;
+    PredColumn* pcols = nullptr;
+    int32_t* status = nullptr;
+    const int nstatus = std::max(npreds, 1) + std::max(npops, 1);
+    DQ_HIP(ctx, buf.alloc((void**)&dslots, sizeof(DictSlot) * nslots));
+    DQ_HIP(ctx, buf.alloc((void**)&dpops, sizeof(DictPredOp) * std::max(npops, 1)));
+    DQ_HIP(ctx, buf.alloc((void**)&dops, sizeof(DictOpMap) * nops));
+    DQ_HIP(ctx, buf.alloc((void**)&dout, sizeof(dq_state) * nops));
+    DQ_HIP(ctx, buf.alloc((void**)&pcols, sizeof(PredColumn) * (size_t)(std::max(ncols, 1) + std::max(npops, 1))));
+    DQ_HIP(ctx, buf.alloc((void**)&status, sizeof(int32_t) * nstatus));
+    const int64_t pwords = padded_words_for(nrows);
+    std::vector<uint64_t*> wt(std::max(npreds, 1), nullptr), wn(std::max(npreds, 1), nullptr);
+    size_t pin = sizeof(DictSlot) * nslots + sizeof(DictPredOp) * std::max(npops, 1) + sizeof(DictOpMap) * nops +
+                 sizeof(dq_state) * nops + sizeof(PredColumn) * (size_t)(std::max(ncols, 1) + std::max(npops, 1)) +
+                 sizeof(int32_t) * nstatus + sizeof(int64_t) * DS_COUNT * nslots + 4096;
+    for (int p = 0; p < npreds; ++p) {
+        if (!where_used[p]) continue;
+        DQ_HIP(ctx, buf.alloc((void**)&wt[p], (size_t)pwords * 8));
+        DQ_HIP(ctx, buf.alloc((void**)&wn[p], (size_t)pwords * 8));
+        pin += pred_stage_bytes(preds[p]);
+    }
+    std::vector<uint64_t*> pt(std::max(npops, 1), nullptr), pn(std::max(npops, 1), nullptr);
+    for (int q = 0; q < npops; ++q) {
+        const int64_t ew = padded_words_for((int64_t)slots[pop_slot[q]].n_dict + 1);
+        DQ_HIP(ctx, buf.alloc((void**)&pt[q], (size_t)ew * 8));
+        DQ_HIP(ctx, buf.alloc((void**)&pn[q], (size_t)ew * 8));
+        pin += pred_stage_bytes(preds[pop_pred[q]]);
+    }
+    int rc = ensure_pinned(ctx, pin);
+    if (rc) return rc;
+    DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the pinned buffer may still feed a previous call's copies
+    Stager up{ctx, Bump()};
+    up.hb.base = ctx->pinned;
+    DQ_HIP(ctx, hipMemsetAsync(zero, 0, zwords * 8, ctx->stream));
+    DQ_HIP(ctx, hipMemsetAsync(status, 0, sizeof(int32_t) * nstatus, ctx->stream));
+    // ---- the where bitmaps over the plain columns ----------------------------------------------------------------
+    std::vector<PredColumn> pc(std::max(ncols, 1) + std::max(npops, 1));
+    memset(pc.data(), 0, sizeof(PredColumn) * pc.size());
+    for (int c = 0; c < ncols; ++c) {
+        if (!(columns[c].flags & DQ_COL_DEVICE)) continue;  // unread (checked above)
+        pc[c].values = columns[c].values;
+        pc[c].validity = (const uint64_t*)columns[c].validity;
+        pc[c].offsets = columns[c].offsets;
+        pc[c].spark_type = columns[c].spark_type;
+        pc[c].elem = elem_of(columns[c].spark_type);
+        pc[c].decimal_scale = columns[c].decimal_scale;
+    }
+    const int pc0 = std::max(ncols, 1);
+    for (int q = 0; q < npops; ++q) {  // each predicate op's single column: its slot's dictionary
+        const dq_column& e = dicts[slot_dict[pop_slot[q]]].dictionary;
+        pc[pc0 + q].values = e.values;
+        pc[pc0 + q].validity = (const uint64_t*)e.validity;
+        pc[pc0 + q].offsets = e.offsets;
+        pc[pc0 + q].spark_type = DQ_TYPE_STRING;
+        pc[pc0 + q].elem = ET_NONE;
+    }
+    if ((rc = up.upload(pcols, pc.data(), sizeof(PredColumn) * pc.size()))) return rc;
+    for (int p = 0; p < npreds; ++p) {
+        if (!where_used[p]) continue;
+        rc = eval_predicate_bits(ctx, preds[p], columns, ncols, pc.data(), pcols, nrows, pwords, wt[p], wn[p], status + p, buf, up);
+        if (rc) return rc;
+    }
+    // ---- the per-row pass: every slot in one launch --------------------------------------------------------------
+    int lds_words = 0;
+    for (int s = 0; s < nslots; ++s) {
+        int64_t* base = zero + zoff[s];
+        slots[s].stats = base;
+        slots[s].fold = base + DS_COUNT;
+        slots[s].counts = base + DS_COUNT + DF_COUNT;
+        slots[s].hll = (uint32_t*)(base + DS_COUNT + DF_COUNT + slots[s].n_dict);
+        slots[s].where_t = slot_where[s] >= 0 ? wt[slot_where[s]] : nullptr;
+        slots[s].where_nn = slot_where[s] >= 0 ? wn[slot_where[s]] : nullptr;
+        slots[s].lds_copies = dict_lds_copies(slots[s].n_dict, nrows, grid);
+        lds_words = std::max(lds_words, slots[s].lds_copies * slots[s].n_dict);
+    }
+    if ((rc = up.upload(dslots, slots.data(), sizeof(DictSlot) * nslots))) return rc;
+    launch_dict_counts(dslots, nslots, nrows, grid, lds_words, ctx->stream);
+    DQ_HIP(ctx, hipGetLastError());
+    ctx->kernel_launches[DQ_KERNEL_DICT_COUNTS]++;
+    // ---- per entry: predicates over the dictionaries, then the fold ----------------------------------------------
+    std::vector<DictPredOp> pops(std::max(npops, 1));
+    for (int q = 0; q < npops; ++q) {
+        const dq_predicate& src = preds[pop_pred[q]];
+        std::vector<int32_t> code(src.code, src.code + std::max(src.code_len, 0));
+        for (size_t k = 0; k + 1 < code.size(); k += 2)
+            if (code[k] == DQ_P_COL) code[k + 1] = 0;  // the dictionary column
+        dq_predicate pr = src;
+        pr.code = code.data();
+        const dq_column& e = dicts[slot_dict[pop_slot[q]]].dictionary;
+        const int64_t ne = e.length;
+        rc = eval_predicate_bits(ctx, pr, &e, 1, pc.data() + pc0 + q, pcols + pc0 + q, ne, padded_words_for(ne), pt[q], pn[q],
+                                 status + std::max(npreds, 1) + q, buf, up);
+        if (rc) return rc;
+        pops[q].pred_t = pt[q];
+        pops[q].pred_nn = pn[q];
+        pops[q].sums = (unsigned long long*)(zero + sums_off + 2 * (size_t)q);
+        pops[q].slot = pop_slot[q];
+        pops[q].pad = 0;
+    }
+    for (int i = 0; i < nops; ++i)
+        if (op_pop[i] >= 0) opmap[i].sums = pops[op_pop[i]].sums;
+    if (npops && (rc = up.upload(dpops, pops.data(), sizeof(DictPredOp) * npops))) return rc;
+    if ((rc = up.upload(dops, opmap.data(), sizeof(DictOpMap) * nops))) return rc;
+    launch_dict_fold(dslots, nslots, max_entries, dpops, npops, ctx->stream);
+    DQ_HIP(ctx, hipGetLastError());
+    ctx->kernel_launches[DQ_KERNEL_DICT_FOLD]++;
+    launch_dict_finalize(dslots, dops, nops, nrows, dout, ctx->stream);
+    DQ_HIP(ctx, hipGetLastError());
+    // ---- results ---------------------------------------------------------------------------------------------
+    dq_state* hout = (dq_state*)up.hb.take(sizeof(dq_state) * nops, 16);
+    int32_t* hstatus = (int32_t*)up.hb.take(sizeof(int32_t) * nstatus, 16);
+    int64_t* hstats = (int64_t*)up.hb.take(sizeof(int64_t) * DS_COUNT * nslots, 16);
+    DQ_HIP(ctx, hipMemcpyAsync(hout, dout, sizeof(dq_state) * nops, hipMemcpyDeviceToHost, ctx->stream));
+    DQ_HIP(ctx, hipMemcpyAsync(hstatus, status, sizeof(int32_t) * nstatus, hipMemcpyDeviceToHost, ctx->stream));
+    for (int s = 0; s < nslots; ++s)
+        DQ_HIP(ctx, hipMemcpyAsync(hstats + DS_COUNT * s, slots[s].stats, sizeof(int64_t) * DS_COUNT, hipMemcpyDeviceToHost, ctx->stream));
+    DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int s = 0; s < nslots; ++s)
+        if (hstats[DS_COUNT * s + DS_BAD_INDEX])
+            return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dictionary column %d: %lld non-NULL rows hold an index outside [0, %d)",
+                        slot_dict[s], (long long)hstats[DS_COUNT * s + DS_BAD_INDEX], slots[s].n_dict);
+    for (int k = 0; k < nstatus; ++k)
+        if (hstatus[k] & 1) return fail(ctx, DQ_ERR_UNSUPPORTED, "dq_dict_scan: regex backtracking limit exceeded");
+    for (int k = 0; k < nstatus; ++k)
+        if (hstatus[k])
+            return fail(ctx, DQ_ERR_UNSUPPORTED,
+                        "dq_dict_scan: a string needs Double.parseDouble's arbitrary-precision path "
+                        "(hexadecimal literal, or > 19 significant digits on a rounding boundary)");
+    memcpy(out, hout, sizeof(dq_state) * nops);
     return DQ_OK;
 }
 

@@ -244,6 +244,33 @@ gather_bytes_kernel(const uint8_t* __restrict__ in, const int32_t* __restrict__ 
     if (g0 + cnt == nsel && lane < 16) out[d1 + lane] = 0;  // the read-past padding of the dword loads
 }
 
+// Decode of a dictionary-encoded column, step 1: the source entry of every row (0 for a NULL row or an index outside
+// the dictionary, which is counted in *bad) and its byte length (0 for those rows; lens[nrows] = 0). Steps 2 and 3 are
+// the string gather's: an exclusive scan into offsets and gather_bytes_kernel with the entries as the source rows.
+__global__ void __launch_bounds__(256)
+dict_lengths_kernel(const int32_t* __restrict__ indices, const uint64_t* __restrict__ valid, const int32_t* __restrict__ dict_offsets,
+                    int32_t n_dict, int64_t nrows, int32_t* __restrict__ src, int64_t* __restrict__ lens,
+                    unsigned long long* __restrict__ bad) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k > nrows) return;
+    int64_t len = 0;
+    if (k < nrows) {
+        const bool on = row_valid(valid, k);
+        const int32_t e = indices[k];
+        const bool ok = on && (uint32_t)e < (uint32_t)n_dict;
+        if (on && !ok) atomicAdd(bad, 1ull);
+        src[k] = ok ? e : 0;
+        len = ok ? dict_offsets[e + 1] - dict_offsets[e] : 0;
+    }
+    lens[k] = len;
+}
+
+__global__ void __launch_bounds__(256)
+narrow_offsets_kernel(const int64_t* __restrict__ wide, int64_t n, int32_t* __restrict__ out) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n) out[k] = (int32_t)wide[k];
+}
+
 }  // namespace dq
 
 namespace {
@@ -492,6 +519,78 @@ int dq_gather_rows(dq_ctx* ctx, const dq_column* column, int64_t nrows, const ui
     DQ_CTX_HIP(ctx, hipMemcpyAsync(&bytes, out_offsets + nselected, sizeof(bytes), hipMemcpyDeviceToHost, s));
     DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
     *out_bytes = bytes;
+    return DQ_OK;
+}
+
+int dq_dict_decode(dq_ctx* ctx, const dq_dict_column* dict, int32_t* out_offsets, void* out_values, int64_t* out_bytes) {
+    if (!ctx || !dict || !out_offsets || !out_bytes || dict->length < 0)
+        return dq::ctx_fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_dict_decode: invalid arguments");
+    if (dq::ctx_num_subs(ctx) != 0)
+        return dq::ctx_fail(ctx, DQ_ERR_UNSUPPORTED, "dq_dict_decode: multi-device contexts are not supported");
+    const dq_column& e = dict->dictionary;
+    const int64_t nrows = dict->length;
+    if (!(dict->flags & DQ_COL_DEVICE) || !(e.flags & DQ_COL_DEVICE) || (e.flags & DQ_COL_OFFSETS64))
+        return dq::ctx_fail(ctx, DQ_ERR_UNSUPPORTED, "dq_dict_decode: device buffers with int32 offsets only");
+    if (e.spark_type != DQ_TYPE_STRING || e.length < 1 || e.length > INT32_MAX - 1 || !e.offsets || !e.values ||
+        (nrows > 0 && !dict->indices))
+        return dq::ctx_fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_dict_decode: the dictionary is a STRING column of n_dict + 1 entries");
+    if (nrows > INT32_MAX) return dq::ctx_fail(ctx, DQ_ERR_UNSUPPORTED, "dq_dict_decode: more than 2^31 - 1 rows");
+    if (((uintptr_t)dict->indices & 3) || ((uintptr_t)dict->validity & 7) || ((uintptr_t)out_offsets & 3))
+        return dq::ctx_fail(ctx, DQ_ERR_ALIGNMENT, "dq_dict_decode: misaligned buffer");
+    const int32_t n_dict = (int32_t)(e.length - 1);
+    *out_bytes = 0;
+    DQ_CTX_HIP(ctx, hipSetDevice(dq::ctx_device(ctx)));
+    hipStream_t s = dq::ctx_stream(ctx);
+    dq::ScratchBuffers buf(ctx);
+    int32_t* src = nullptr;
+    int64_t *lens = nullptr, *wide = nullptr;
+    unsigned long long* bad = nullptr;
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&src, sizeof(int32_t) * (size_t)std::max<int64_t>(nrows, 1)));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&lens, sizeof(int64_t) * (size_t)(nrows + 1)));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&wide, sizeof(int64_t) * (size_t)(nrows + 1)));
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&bad, sizeof(unsigned long long)));
+    DQ_CTX_HIP(ctx, hipMemsetAsync(bad, 0, sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(dq::dict_lengths_kernel, dim3(blocks_of(nrows + 1)), dim3(256), 0, s, dict->indices,
+                       (const uint64_t*)dict->validity, e.offsets, n_dict, nrows, src, lens, bad);
+    DQ_CTX_HIP(ctx, hipGetLastError());
+    size_t tb = 0;
+    DQ_CTX_HIP(ctx, rocprim::exclusive_scan(nullptr, tb, lens, wide, (int64_t)0, (size_t)(nrows + 1), rocprim::plus<int64_t>(), s));
+    void* tmp = nullptr;
+    DQ_CTX_HIP(ctx, buf.alloc(&tmp, tb));
+    DQ_CTX_HIP(ctx, rocprim::exclusive_scan(tmp, tb, lens, wide, (int64_t)0, (size_t)(nrows + 1), rocprim::plus<int64_t>(), s));
+    int64_t total = 0;
+    unsigned long long nbad = 0;
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(&total, wide + nrows, sizeof(total), hipMemcpyDeviceToHost, s));
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(&nbad, bad, sizeof(nbad), hipMemcpyDeviceToHost, s));
+    DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
+    if (nbad) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "dq_dict_decode: %llu non-NULL rows hold an index outside [0, %d)", nbad, n_dict);
+        return dq::ctx_fail(ctx, DQ_ERR_INVALID_ARGUMENT, msg);
+    }
+    if (total >= ((int64_t)1 << 31)) {
+        char msg[200];
+        snprintf(msg, sizeof(msg), "dq_dict_decode: the decoded strings hold %lld bytes, past the int32 offsets of one "
+                 "column (2^31): keep the column encoded or split the rows", (long long)total);
+        return dq::ctx_fail(ctx, DQ_ERR_UNSUPPORTED, msg);
+    }
+    *out_bytes = total;
+    if (!out_values) {  // sizing call: the offsets
+        hipLaunchKernelGGL(dq::narrow_offsets_kernel, dim3(blocks_of(nrows + 1)), dim3(256), 0, s, wide, nrows + 1, out_offsets);
+        DQ_CTX_HIP(ctx, hipGetLastError());
+        DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
+        return DQ_OK;
+    }
+    // copy call: out_offsets holds the sizing call's offsets; out_values has their total + 16 bytes
+    if (nrows == 0) {
+        DQ_CTX_HIP(ctx, hipMemsetAsync(out_values, 0, 16, s));
+    } else {
+        hipLaunchKernelGGL(dq::gather_bytes_kernel, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, s,
+                           (const uint8_t*)e.values, e.offsets, src, out_offsets, nrows, (uint8_t*)out_values);
+        DQ_CTX_HIP(ctx, hipGetLastError());
+    }
+    ctx->kernel_launches[DQ_KERNEL_DICT_DECODE]++;
+    DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
     return DQ_OK;
 }
 

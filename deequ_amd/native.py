@@ -61,7 +61,7 @@ HLL_NUM_WORDS = 52
 FREQ_PATHS = ("fast", "fast_narrow", "fast_done", "exact", "partitioned", "sorted", "small", "small_optimistic", "fast_spill",
               "split_buckets", "long_tuples")
 SCAN_KERNELS = ("striped", "striped_heavy", "heavy8", "heavy8_full", "bits", "pred_simple", "pred_vm", "regex",
-                "strings", "where_fused", "where_masks", "decimal128")
+                "strings", "where_fused", "where_masks", "decimal128", "dict_counts", "dict_fold", "dict_decode")
 
 # Every symbol include/dq.h declares (checked by tests/test_native_abi.py).
 EXPORTED_SYMBOLS = (
@@ -75,6 +75,7 @@ EXPORTED_SYMBOLS = (
     "dq_kll_merge_states", "dq_scratch_trim", "dq_frequencies_parts", "dq_set_priority",
     "dq_schema_validate", "dq_schema_launch_count", "dq_gather_rows", "dq_parse_int32", "dq_parse_decimal",
     "dq_parse_timestamp", "dq_split_rows", "dq_split_row_is_test", "dq_dec128_to_double",
+    "dq_dict_scan", "dq_dict_counts", "dq_dict_decode",
 )
 
 
@@ -82,6 +83,12 @@ class DqColumn(ctypes.Structure):
     _fields_ = [("spark_type", ctypes.c_int32), ("flags", ctypes.c_uint32), ("length", ctypes.c_int64),
                 ("values", ctypes.c_void_p), ("validity", ctypes.c_void_p), ("offsets", ctypes.c_void_p),
                 ("decimal_precision", ctypes.c_int32), ("decimal_scale", ctypes.c_int32)]
+
+
+class DqDictColumn(ctypes.Structure):
+    """dq_dict_column: a dictionary-encoded STRING column (device buffers)."""
+    _fields_ = [("flags", ctypes.c_uint32), ("pad", ctypes.c_uint32), ("length", ctypes.c_int64),
+                ("indices", ctypes.c_void_p), ("validity", ctypes.c_void_p), ("dictionary", DqColumn)]
 
 
 class DqConst(ctypes.Structure):
@@ -322,6 +329,10 @@ def load_library(path=None):
                                       c_void_p, c_void_p]),
             "dq_split_row_is_test": (c_int, [c_int64, ctypes.c_uint64, ctypes.c_double]),
             "dq_dec128_to_double": (ctypes.c_double, [c_void_p, ctypes.c_int32]),
+            "dq_dict_scan": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p,
+                                     c_int, c_void_p]),
+            "dq_dict_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+            "dq_dict_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name)
@@ -510,6 +521,35 @@ class Context:
         rc = self.lib.dq_scan(self.handle, col_arr, ncol, int(nrows), op_arr, len(ops), pred_arr, len(preds), out, 0)
         self.check(rc, "dq_scan")
         return [out[i] for i in range(len(ops))]
+
+    def dict_scan(self, columns, dicts, nrows, ops, preds):
+        """Run dq_dict_scan: ops over dictionary-encoded columns (`dicts`: list of DqDictColumn; an op's column index
+        len(columns) + d names dicts[d]). Returns a list of DqState (host)."""
+        col_arr = (DqColumn * max(len(columns), 1))(*columns)
+        dict_arr = (DqDictColumn * max(len(dicts), 1))(*dicts)
+        op_arr = (DqOp * max(len(ops), 1))(*ops)
+        pred_arr = (DqPredicate * max(len(preds), 1))(*preds)
+        out = (DqState * max(len(ops), 1))()
+        rc = self.lib.dq_dict_scan(self.handle, col_arr, len(columns), dict_arr, len(dicts), int(nrows), op_arr, len(ops),
+                                   pred_arr, len(preds), out)
+        self.check(rc, "dq_dict_scan")
+        return [out[i] for i in range(len(ops))]
+
+    def dict_counts(self, dict_column, counts_dev_ptr):
+        """dq_dict_counts: the per-entry row counts into counts_dev_ptr (n_dict int64); returns (rows, non-NULL rows)."""
+        rows = (ctypes.c_int64 * 2)()
+        rc = self.lib.dq_dict_counts(self.handle, ctypes.byref(dict_column), ctypes.c_void_p(counts_dev_ptr), rows)
+        self.check(rc, "dq_dict_counts")
+        return int(rows[0]), int(rows[1])
+
+    def dict_decode(self, dict_column, offsets_ptr, values_ptr=None):
+        """dq_dict_decode: the sizing call (values_ptr None: writes the offsets) or the copy call; returns the decoded
+        byte count."""
+        nbytes = ctypes.c_int64(0)
+        rc = self.lib.dq_dict_decode(self.handle, ctypes.byref(dict_column), ctypes.c_void_p(offsets_ptr),
+                                     ctypes.c_void_p(values_ptr) if values_ptr else None, ctypes.byref(nbytes))
+        self.check(rc, "dq_dict_decode")
+        return int(nbytes.value)
 
     def scan_streamed(self, columns, nrows, ops, preds, chunk_rows):
         """dq_scan_streamed: host columns streamed through HBM in row chunks (copy / scan overlapped)."""

@@ -339,8 +339,11 @@ class ColumnProfiler:
         value formatted as `row.get(index).toString`, ratio = count / rows."""
         from . import engine
         out = {}
+        from .analyzers import dictionary_frequencies
         for name in targets:
-            table = engine.frequencies(data, [name], include_nulls=True)
+            table = dictionary_frequencies(data, name, include_nulls=True)  # a kept dictionary column: per entry
+            if table is None:
+                table = engine.frequencies(data, [name], include_nulls=True)
             counts = table.to_dict()
             total = sum(counts.values())
             values = {}
@@ -371,8 +374,12 @@ def _chunked_histograms(data, targets):
     out = {}
     for name in targets:
         counts = {}
+        from .analyzers import dictionary_frequencies
         for chunk in data.chunks:
-            for key, c in engine.frequencies(chunk, [name], include_nulls=True).to_dict().items():
+            table = dictionary_frequencies(chunk, name, include_nulls=True)
+            if table is None:
+                table = engine.frequencies(chunk, [name], include_nulls=True)
+            for key, c in table.to_dict().items():
                 counts[key] = counts.get(key, 0) + int(c)
         total = sum(counts.values())
         values = {}

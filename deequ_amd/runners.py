@@ -16,7 +16,7 @@ from .analyzers import (Analyzer, ScanShareableAnalyzer, GroupingAnalyzer, ScanS
 from .analyzers import merge as merge_states
 from .expr import compile_predicate
 from .metrics import DoubleMetric, Success, UnsupportedOnDevice
-from .table import ChunkedTable
+from .table import ChunkedTable, DictColumn
 
 
 def stream_chunk_rows():
@@ -217,8 +217,77 @@ class ScanBatch:
             self.quantile_index[key] = len(self.quantile_reqs) - 1
         return self.quantile_index[key]
 
-    def native_columns(self):
-        return [self.data[n].native() for n in self.names]
+    def native_columns(self, decoded=None):
+        """The batch's columns for the C-ABI. A dictionary-encoded column (DictColumn) goes as its decoded STRING
+        column; with `decoded` (a set of names) only the kept device columns named there do, and the others -- which no
+        op of the call reads -- go as the INT column of their indices, so that nothing is decoded for them."""
+        out = []
+        for n in self.names:
+            c = self.data[n]
+            if decoded is not None and isinstance(c, DictColumn) and c.dict_device is not None and n not in decoded:
+                out.append(c.indices_native())
+            else:
+                out.append(c.native())
+        return out
+
+    _DICT_COLUMN_OPS = (N.OP_COMPLETENESS, N.OP_MIN_LENGTH, N.OP_MAX_LENGTH, N.OP_APPROX_COUNT_DISTINCT, N.OP_DATATYPE)
+
+    def _pred_columns(self, p):
+        """Names of the columns predicate p reads (-1: none)."""
+        if p < 0:
+            return set()
+        code = self.preds[p]._code
+        return {self.names[int(a)] for op, a in zip(code[0::2], code[1::2]) if int(op) == N.P_COL}
+
+    def _dict_plan(self):
+        """(plain op indices, dictionary op indices, names of kept columns the plain call decodes), or None when the
+        batch has no device-resident dictionary-encoded column or runs on a multi-device context. An op goes to
+        dq_dict_scan when it reads one kept column natively: a column op of _DICT_COLUMN_OPS, or a Compliance /
+        PatternMatch whose predicate reads only that column -- under no `where` or one over plain columns. Every
+        other op that touches a kept column reads it decoded, in the plain dq_scan call."""
+        kept = {n for n in self.names if isinstance(self.data[n], DictColumn) and self.data[n].dict_device is not None}
+        if not kept or getattr(engine.ctx(), "multi", False):
+            return None
+        plain, native, decoded = [], [], set()
+        for i, op in enumerate(self.ops):
+            reads = {self.names[c] for c in (op.column[0], op.column[1]) if c >= 0}
+            where_cols, pred_cols = self._pred_columns(op.where), self._pred_columns(op.predicate)
+            is_native = not (where_cols & kept) and all(self.data[c].device is not None for c in where_cols) and (
+                (op.kind in self._DICT_COLUMN_OPS and reads <= kept and len(reads) == 1) or
+                (op.kind == N.OP_COMPLIANCE and len(pred_cols) == 1 and pred_cols <= kept))
+            if is_native:
+                native.append(i)
+            else:
+                plain.append(i)
+                decoded |= (reads | where_cols | pred_cols) & kept
+        return plain, native, decoded
+
+    def _run_with_dictionaries(self, plan):
+        """The plain ops through dq_scan as ever, the dictionary ops through one dq_dict_scan call."""
+        plain, native, decoded = plan
+        ctx = engine.ctx()
+        cols = self.native_columns(decoded)
+        preds = [p.to_native() for p in self.preds]
+        states = [None] * len(self.ops)
+        if plain:
+            for i, st in zip(plain, ctx.scan(cols, self.data.nrows, [self.ops[i] for i in plain], preds)):
+                states[i] = st
+        if native:
+            dict_names, dops = [], []
+            for i in native:
+                src = self.ops[i]
+                name = self.names[src.column[0]] if src.kind != N.OP_COMPLIANCE else \
+                    next(iter(self._pred_columns(src.predicate)))
+                if name not in dict_names:
+                    dict_names.append(name)
+                op = N.DqOp()
+                op.kind, op.where, op.predicate = src.kind, src.where, src.predicate
+                op.column[0], op.column[1] = len(cols) + dict_names.index(name), -1
+                dops.append(op)
+            dicts = [self.data[n].native_dict() for n in dict_names]
+            for i, st in zip(native, ctx.dict_scan(cols, dicts, self.data.nrows, dops, preds)):
+                states[i] = st
+        return states
 
     def _streamed(self):
         """The batch goes through dq_scan_streamed: a host-resident table larger than the configured row chunk."""
@@ -230,7 +299,10 @@ class ScanBatch:
         if self.ops:
             chunk = stream_chunk_rows()
             host = all(self.data[n].device is None for n in self.names)
-            if chunk and host and out_device_ptr is None and self.data.nrows > chunk:
+            plan = self._dict_plan() if out_device_ptr is None else None
+            if plan is not None:
+                got = self._run_with_dictionaries(plan)
+            elif chunk and host and out_device_ptr is None and self.data.nrows > chunk:
                 # host-resident table streamed through HBM in row chunks (dq_scan_streamed)
                 got = engine.ctx().scan_streamed(self.native_columns(), self.data.nrows, self.ops,
                                                  [p.to_native() for p in self.preds], chunk)

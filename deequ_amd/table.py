@@ -283,6 +283,209 @@ class PartedColumn(Column):
         return out
 
 
+class _DecodedBuffers:
+    """The device buffers of a DictColumn as a plain STRING column's `device` dict: present (so `col.device is not
+    None` costs nothing) but decoded, on the device, only when a buffer is asked for."""
+
+    def __init__(self, col):
+        self._col = col
+
+    def _d(self):
+        return self._col.decoded().device
+
+    def __getitem__(self, key):
+        return self._d()[key]
+
+    def get(self, key, default=None):
+        return self._d().get(key, default)
+
+    def __contains__(self, key):
+        return key in self._d()
+
+    def keys(self):
+        return self._d().keys()
+
+    def items(self):
+        return self._d().items()
+
+
+class DictColumn(Column):
+    """A STRING column held dictionary-encoded (Arrow `dictionary<values=string, indices=int32>`): int32 `indices`
+    into `dictionary`, a plain STRING Column of n_dict entries that may hold duplicates, unused entries, the empty
+    string and NULL entries. A row is NULL iff its validity bit is clear: the rows that point at a NULL entry are
+    folded into the bitmap at ingest, and the index of a NULL row is 0. The indices and the dictionary always have
+    host buffers (the dictionary is small); `to_device` adds the HBM copies the native paths read (dq_dict_scan,
+    dq_dict_counts). Every consumer that does not know the class sees a plain STRING column: `values`, `offsets`,
+    `device` and `native()` are those of `decoded()`, built on first use (on the device for a device column)."""
+
+    def __init__(self, name, indices, validity, dictionary):
+        self.name = name
+        self.spark_type = N.TYPE_STRING
+        self.indices = np.ascontiguousarray(indices, dtype=np.int32)
+        self.validity = validity
+        self.dictionary = dictionary
+        self.decimal_precision = 0
+        self.decimal_scale = 0
+        self.length = len(self.indices)
+        self.dict_device = None  # torch tensors once resident: indices, validity, dict_values, dict_offsets, dict_validity
+        self.tz = None
+        self._decoded = None
+
+    @property
+    def n_dict(self):
+        return self.dictionary.length
+
+    # ---- the plain-column view -------------------------------------------------------------------
+    @property
+    def values(self):
+        return None if self.dict_device is not None else self.decoded().values  # a device column decodes in HBM only
+
+    @property
+    def offsets(self):
+        return None if self.dict_device is not None else self.decoded().offsets
+
+    @property
+    def device(self):
+        return _DecodedBuffers(self) if self.dict_device is not None else None
+
+    def native(self):
+        return self.decoded().native()
+
+    def decoded(self):
+        """The column as a plain STRING Column (cached): host buffers for a host column; for a device column a
+        device-only column gathered in HBM (dq_dict_decode), sharing this column's validity bitmap."""
+        if self._decoded is None:
+            self._decoded = self._decode_device() if self.dict_device is not None else self._decode_host()
+        return self._decoded
+
+    def _decode_host(self):
+        d = self.dictionary
+        doff = np.asarray(d.offsets, dtype=np.int64)
+        if self.length == 0 or d.length == 0:
+            return Column(self.name, N.TYPE_STRING, np.zeros(0, np.uint8), self.validity,
+                          np.zeros(self.length + 1, np.int32), length=self.length)
+        idx = self.indices.astype(np.int64)
+        lens = doff[idx + 1] - doff[idx]
+        lens[~unpack_validity(self.validity, self.length)] = 0
+        offs = np.zeros(self.length + 1, dtype=np.int64)
+        np.cumsum(lens, out=offs[1:])
+        if offs[-1] >= 2 ** 31:
+            raise ValueError("column %s: the decoded strings hold %d bytes, past the int32 offsets of one column (2^31)"
+                             % (self.name, int(offs[-1])))
+        src = np.repeat(doff[idx] - offs[:-1], lens) + np.arange(int(offs[-1]), dtype=np.int64)
+        data = np.asarray(d.values, dtype=np.uint8)[src]
+        return Column(self.name, N.TYPE_STRING, data, self.validity, offs.astype(np.int32), length=self.length)
+
+    def _decode_device(self):
+        import torch
+        from . import engine
+        dd = self.dict_device
+        dev = dd["indices"].device
+        offsets = torch.empty(self.length + 1, dtype=torch.int32, device=dev)
+        ctx = engine.ctx()
+        total = ctx.dict_decode(self.native_dict(), offsets.data_ptr(), None)
+        values = torch.empty(total + 16, dtype=torch.uint8, device=dev)
+        ctx.dict_decode(self.native_dict(), offsets.data_ptr(), values.data_ptr())
+        col = Column(self.name, N.TYPE_STRING, None, None, length=self.length)
+        col.device = {"values": values, "offsets": offsets}
+        if dd.get("validity") is not None:
+            col.device["validity"] = dd["validity"]
+        return col
+
+    # ---- cells -------------------------------------------------------------------------------------
+    def valid_at(self, i):
+        return True if self.validity is None else bool((self.validity[i >> 3] >> (i & 7)) & 1)
+
+    def value_at(self, i):
+        return self.dictionary.value_at(int(self.indices[i]))
+
+    def cells_at(self, rows):
+        return [self.value_at(int(r)) if self.valid_at(int(r)) else None for r in np.asarray(rows, dtype=np.int64)]
+
+    def to_pylist(self):
+        entries = self.dictionary.to_pylist()
+        valid = unpack_validity(self.validity, self.length)
+        return [entries[i] if v else None for i, v in zip(self.indices.tolist(), valid.tolist())]
+
+    def to_arrow(self):
+        import pyarrow as pa
+        return column_to_arrow(self, pa)
+
+    # ---- device ------------------------------------------------------------------------------------
+    def to_device(self, device=0):
+        """Copy the indices, the validity bitmap and the dictionary into HBM. The device dictionary holds one entry
+        more than `dictionary`: entry n_dict is NULL and stands for the NULL rows when a predicate is evaluated once
+        per entry (dq_dict_scan)."""
+        import torch
+        dev = torch.device("cuda", device) if not isinstance(device, torch.device) else device
+        d, nd = self.dictionary, self.dictionary.length
+        dd = {"indices": torch.from_numpy(self.indices).to(dev)}
+        if self.validity is not None:
+            dd["validity"] = torch.from_numpy(pack_validity(unpack_validity(self.validity, self.length))).to(dev)
+        offs = np.asarray(d.offsets, dtype=np.int32)[:nd + 1] if nd else np.zeros(1, np.int32)
+        nbytes = int(offs[-1])
+        dd["dict_values"] = torch.from_numpy(
+            np.concatenate([np.asarray(d.values, dtype=np.uint8)[:nbytes], np.zeros(16, np.uint8)])).to(dev)
+        dd["dict_offsets"] = torch.from_numpy(np.concatenate([offs, offs[-1:]]).astype(np.int32)).to(dev)
+        dvalid = np.concatenate([unpack_validity(d.validity, nd), np.zeros(1, dtype=bool)])
+        dd["dict_validity"] = torch.from_numpy(pack_validity(dvalid)).to(dev)
+        self.dict_device = dd
+        self._decoded = None
+        return self
+
+    def native_dict(self):
+        """DqDictColumn over the device buffers (the C-ABI's dq_dict_column)."""
+        dd = self.dict_device
+        if dd is None:
+            raise TypeError("column %s: the dictionary paths read device-resident columns (to_device())" % self.name)
+        c = N.DqDictColumn()
+        c.flags = N.COL_DEVICE
+        c.length = self.length
+        c.indices = dd["indices"].data_ptr()
+        c.validity = dd["validity"].data_ptr() if dd.get("validity") is not None else None
+        c.dictionary.spark_type = N.TYPE_STRING
+        c.dictionary.flags = N.COL_DEVICE
+        c.dictionary.length = self.n_dict + 1
+        c.dictionary.values = dd["dict_values"].data_ptr()
+        c.dictionary.offsets = dd["dict_offsets"].data_ptr()
+        c.dictionary.validity = dd["dict_validity"].data_ptr()
+        return c
+
+    def indices_native(self):
+        """The indices as an INT column: how the fused scan is handed a kept column that none of its ops reads."""
+        c = N.DqColumn()
+        c.spark_type = N.TYPE_INT
+        c.flags = N.COL_DEVICE
+        c.length = self.length
+        c.values = self.dict_device["indices"].data_ptr()
+        c.validity = self.dict_device["validity"].data_ptr() if self.dict_device.get("validity") is not None else None
+        return c
+
+
+def _dict_column_from_arrow(name, arr, pa):
+    """dictionary<values=string|large_string, indices=intN|uintN> -> DictColumn: the indices widened to int32 (a
+    cast, never a decode), NULL entries folded into the validity bitmap, an index outside the dictionary on a valid
+    row rejected."""
+    n = len(arr)
+    entries = arr.dictionary
+    if pa.types.is_large_string(entries.type):
+        entries = entries.cast(pa.string())
+    dictionary = _column_from_arrow(name, entries, pa)
+    nd = dictionary.length
+    ind = arr.indices
+    valid = ~np.asarray(ind.is_null()) if ind.null_count else np.ones(n, dtype=bool)
+    idx = np.asarray(ind.fill_null(0) if ind.null_count else ind).astype(np.int64)
+    bad = valid & ((idx < 0) | (idx >= nd))
+    if bad.any():
+        r = int(np.flatnonzero(bad)[0])
+        raise ValueError("column %s: row %d has dictionary index %d outside [0, %d)" % (name, r, int(idx[r]), nd))
+    idx[~valid] = 0
+    if dictionary.validity is not None and n:
+        valid &= unpack_validity(dictionary.validity, nd)[idx] if nd else False
+        idx[~valid] = 0
+    return DictColumn(name, idx.astype(np.int32), None if valid.all() else pack_validity(valid), dictionary)
+
+
 def _wide_column_from_pylist(name, precision, scale, items):
     """decimal.Decimal / int / str cells -> a DECIMAL128 column of decimal(precision, scale); a cell that does not fit
     (more fraction digits than the scale, or more than `precision` digits) raises ValueError."""
@@ -351,8 +554,15 @@ def _arrow_validity(arr, n):
     return pack_validity(mask)
 
 
-def _column_from_arrow(name, arr, pa, wide_decimals=False):
+def _kept_dictionary(t, pa):
+    """The Arrow type is one that `dictionaries="keep"` holds encoded: a dictionary of strings."""
+    return pa.types.is_dictionary(t) and (pa.types.is_string(t.value_type) or pa.types.is_large_string(t.value_type))
+
+
+def _column_from_arrow(name, arr, pa, wide_decimals=False, dictionaries="decode"):
     t, n = arr.type, len(arr)
+    if dictionaries == "keep" and _kept_dictionary(t, pa):
+        return _dict_column_from_arrow(name, arr, pa)
     validity = _arrow_validity(arr, n)
     if pa.types.is_dictionary(t):
         return _column_from_arrow(name, arr.dictionary_decode(), pa, wide_decimals)
@@ -409,6 +619,9 @@ def column_to_arrow(col, pa):
     mask = None if valid.all() else ~valid
     vbuf = None if mask is None else pa.py_buffer(np.packbits(valid, bitorder="little").tobytes())
     t = col.spark_type
+    if isinstance(col, DictColumn):  # round-trips as a dictionary array (the entries as they are)
+        ind = pa.array(col.indices[:n], type=pa.int32(), mask=mask)
+        return pa.DictionaryArray.from_arrays(ind, column_to_arrow(col.dictionary, pa))
     if t == N.TYPE_STRING:
         off = np.ascontiguousarray(np.asarray(col.offsets, dtype=np.int32)[:n + 1])
         data = np.ascontiguousarray(np.asarray(col.values, dtype=np.uint8)[:int(off[-1]) if n else 0])
@@ -507,26 +720,46 @@ class Table:
         return cls(cols)
 
     @classmethod
-    def from_arrow(cls, table, wide_decimals=False):
+    def from_arrow(cls, table, wide_decimals=False, dictionaries="decode"):
         """pyarrow.Table (a Spark DataFrame collected through Arrow, or a parquet read) -> Table.
         Fixed-width values and UTF-8 offsets/data are taken from the Arrow buffers without a
         per-row pass; validity bitmaps are realigned to bit 0 and padded; booleans are widened to one
         byte per row, timestamps normalised to Spark's microseconds, decimals (precision <= 18) to
         unscaled longs. decimal128(p > 18, s) columns raise unless `wide_decimals`: then they load as 128-bit
         decimal columns (DQ_TYPE_DECIMAL128, the Arrow cells as they are), which the fused scan and the cast accept;
-        every other analyzer over such a column fails alone."""
+        every other analyzer over such a column fails alone.
+        `dictionaries`: "decode" (default) rebuilds every row of a dictionary-encoded column on the host; "keep" holds
+        dictionary<string> columns encoded (DictColumn: int32 indices + the dictionary; chunks with different
+        dictionaries are unified), which device-resident tables scan and group without decoding. Dictionaries of
+        other value types decode either way."""
         import pyarrow as pa
+        if dictionaries not in ("decode", "keep"):
+            raise ValueError("dictionaries must be 'decode' or 'keep', not %r" % (dictionaries,))
         cols = []
         for name, chunked in zip(table.column_names, table.columns):
+            if dictionaries == "keep" and chunked.num_chunks > 1 and _kept_dictionary(chunked.type, pa):
+                chunked = chunked.unify_dictionaries()
             arr = chunked.combine_chunks() if chunked.num_chunks != 1 else chunked.chunk(0)
-            cols.append(_column_from_arrow(name, arr, pa, wide_decimals))
+            if isinstance(arr, pa.ChunkedArray):  # a column without chunks
+                arr = arr.chunk(0) if arr.num_chunks == 1 else pa.array([], type=chunked.type)
+            cols.append(_column_from_arrow(name, arr, pa, wide_decimals, dictionaries))
         return cls(cols)
 
     @classmethod
-    def from_parquet(cls, path, columns=None, wide_decimals=False):
-        """Parquet file or directory -> Table (through pyarrow, then `from_arrow`)."""
+    def from_parquet(cls, path, columns=None, wide_decimals=False, dictionaries="decode"):
+        """Parquet file or directory -> Table (through pyarrow, then `from_arrow`). dictionaries="keep" reads the
+        string columns dictionary-encoded (`read_dictionary`) and holds them so."""
+        import pyarrow as pa
         import pyarrow.parquet as pq
-        return cls.from_arrow(pq.read_table(path, columns=columns), wide_decimals=wide_decimals)
+        if dictionaries == "keep":
+            schema = pq.ParquetDataset(path).schema
+            strings = [f.name for f in schema if (pa.types.is_string(f.type) or pa.types.is_large_string(f.type) or
+                                                  _kept_dictionary(f.type, pa)) and
+                       (columns is None or f.name in columns)]
+            return cls.from_arrow(pq.read_table(path, columns=columns, read_dictionary=strings),
+                                  wide_decimals=wide_decimals, dictionaries="keep")
+        return cls.from_arrow(pq.read_table(path, columns=columns), wide_decimals=wide_decimals,
+                              dictionaries=dictionaries)
 
     # ---- schema / access ------------------------------------------------------------------------
     @property
@@ -569,6 +802,9 @@ class Table:
         import torch
         dev = torch.device("cuda", device)
         for c in self.columns.values():
+            if isinstance(c, DictColumn):
+                c.to_device(dev)
+                continue
             d = {}
             if c.spark_type == N.TYPE_STRING:
                 d["values"] = torch.from_numpy(np.concatenate([c.values, np.zeros(16, np.uint8)])).to(dev)
@@ -643,6 +879,9 @@ class ChunkedTable:
         DQ_GROUP_CONCAT=1 always concatenates."""
         import os
         cols = [self.chunks[0][n] for n in names]
+        if len(names) == 1 and all(isinstance(ch[names[0]], DictColumn) and ch[names[0]].dict_device is not None
+                                   for ch in self.chunks):
+            return self.parted(names)  # dictionary-encoded chunks: counted per chunk, their entries built once
         if len(self.chunks) == 2 and not os.environ.get("DQ_GROUP_CONCAT") and \
                 any(c.spark_type == N.TYPE_STRING for c in cols) and \
                 all(ch[n].device is not None and not getattr(ch[n], "offsets64", False)

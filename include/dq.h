@@ -324,9 +324,59 @@ typedef enum dq_scan_kernel {
     DQ_KERNEL_WHERE_FUSED = 9,    /* a value scan that also evaluates a `where` and writes its masks              */
     DQ_KERNEL_WHERE_MASKS = 10,   /* where_masks_kernel: a `where` into per-column masks (no fused producer)       */
     DQ_KERNEL_DECIMAL128 = 11,    /* scan_decimal128_kernel: every (DECIMAL128 column, where) slot of a call      */
-    DQ_KERNEL_COUNT = 12
+    DQ_KERNEL_DICT_COUNTS = 12,   /* dict_counts_kernel: every (dictionary column, where) slot of a call          */
+    DQ_KERNEL_DICT_FOLD = 13,     /* dict_fold_kernel: the per-entry fold of a dq_dict_scan call                  */
+    DQ_KERNEL_DICT_DECODE = 14,   /* dq_dict_decode calls that copied bytes (a kept column handed on decoded)     */
+    DQ_KERNEL_COUNT = 15
 } dq_scan_kernel;
 int64_t dq_scan_kernel_launches(const dq_ctx* ctx, int32_t kernel);
+
+/* ---------------------------------------------------------------------------------------------
+ * Dictionary-encoded STRING columns (Arrow dictionary<values=string, indices=int32>, as parquet writes categorical
+ * strings): kept encoded on the GPU. Every answer below is a function of the dictionary entries and of how many rows
+ * under the `where` point at each entry, so the per-row pass is a 4-byte index histogram (dict_counts_kernel) and
+ * lengths, DataType classes, XXH64 and predicates run once per entry. Single-device contexts, device buffers.
+ *   - Row i is NULL iff its validity bit is clear. The caller folds rows that point at a NULL entry into the bitmap;
+ *     the index of a NULL row is not read as an address but must be readable memory.
+ *   - `dictionary` is a STRING dq_column of n_dict + 1 entries (int32 offsets, a validity bitmap, bytes 4-B aligned
+ *     with >= 16 readable bytes past the end): entries [0, n_dict) are the dictionary -- duplicates, unused entries,
+ *     NULL entries and the empty string are fine -- and entry n_dict is NULL. It stands for the NULL rows when a
+ *     predicate is evaluated once per entry (`c IS NULL` is TRUE there).
+ *   - An index outside [0, n_dict) on a non-NULL row fails the call with DQ_ERR_INVALID_ARGUMENT; it is never used as
+ *     an address.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct dq_dict_column {
+    uint32_t flags;            /* DQ_COL_DEVICE (required)                                       */
+    uint32_t pad;
+    int64_t length;            /* rows                                                           */
+    const int32_t* indices;    /* `length` indices, 4-B aligned                                  */
+    const uint8_t* validity;   /* Arrow LSB-first bitmap, 8-B aligned and whole 8-byte words, or NULL */
+    dq_column dictionary;      /* see above: length = n_dict + 1                                 */
+} dq_dict_column;
+
+/* The states dq_scan would write over the decoded columns, from one dict_counts_kernel launch over every
+ * (dictionary column, where) slot of the call plus one per-entry fold. ops[i].column[0] = ncols + d names dicts[d].
+ * Kinds: COMPLETENESS, MIN_LENGTH, MAX_LENGTH, APPROX_COUNT_DISTINCT, DATATYPE, and COMPLIANCE whose predicate reads
+ * only that dictionary column and constants (every DQ_P_COL of it is taken as the dictionary column, whatever its
+ * arg; [COL, REGEX] programs are PatternMatch): the predicate is evaluated over the n_dict + 1 entries by the kernels
+ * dq_scan uses, and the counts are summed under its TRUE bitmap. ops[i].where indexes `preds` and reads `columns`
+ * (plain device columns of nrows rows) only. `out` is host memory. Anything else: DQ_ERR_UNSUPPORTED. */
+int dq_dict_scan(dq_ctx* ctx, const dq_column* columns, int ncols, const dq_dict_column* dicts, int ndicts, int64_t nrows,
+                 const dq_op* ops, int nops, const dq_predicate* preds, int npreds, dq_state* out);
+
+/* counts_dev[e] (n_dict int64, device) = non-NULL rows of `dict` that point at entry e; rows[0] = the column's rows,
+ * rows[1] = its non-NULL rows (host). The grouping analyzers over one dictionary column build their frequency table
+ * from (entries with a count > 0, counts) with dq_frequencies_ex weights; duplicate entries add up there. Exact
+ * (integer atomics), also past 2^32 rows per entry. DQ_DICT_LDS_ENTRIES (read per call, default 16384, at most 16384):
+ * dictionaries of up to that many entries count in workgroup-private LDS counters, larger ones with 64-bit global
+ * atomics. DQ_DICT_LDS_COPIES (1, 2 or 4; measurements only) lowers the number of LDS counter copies from 8. */
+int dq_dict_counts(dq_ctx* ctx, const dq_dict_column* dict, int64_t* counts_dev, int64_t* rows);
+
+/* Decode on the device: the plain STRING column of the same rows. Two calls, as dq_gather_rows: with out_values ==
+ * NULL, writes out_offsets (length + 1 int32, device; a NULL row is empty) and *out_bytes; then with out_values
+ * (>= *out_bytes + 16 bytes) and the same out_offsets, copies the bytes and zeroes the 16 bytes after them. The rows'
+ * validity bitmap is the dictionary column's own. DQ_ERR_UNSUPPORTED when the decoded bytes would reach 2^31. */
+int dq_dict_decode(dq_ctx* ctx, const dq_dict_column* dict, int32_t* out_offsets, void* out_values, int64_t* out_bytes);
 
 /* Which grouping build produced the frequency tables of this context so far (all devices of a multi-device
  * context), so a test can prove which path it checked against the oracle (tests/test_gpu_grouping_oracle.py). */
