@@ -25,6 +25,7 @@
 #include "dq_dict.h"
 #include "dq_internal.h"
 #include "rx_engine.h"
+#include "scan_plan.h"
 
 #include <execinfo.h>
 #include <signal.h>
@@ -49,9 +50,7 @@ struct DqSegvTrace {
 } dq_segv_trace_init;
 }  // namespace
 
-
 using namespace dq;
-
 
 namespace {
 
@@ -72,8 +71,6 @@ int fail(dq_ctx* ctx, int code, const char* fmt, ...) {
             return fail((ctx), DQ_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_));     \
     } while (0)
 
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 // DQ_PRED_VM=1: every predicate on the general VM (A/B and cross-checks of the simple-predicate kernel).
 bool pred_vm_forced() {
     const char* e = getenv("DQ_PRED_VM");
@@ -93,124 +90,6 @@ int64_t scan_grid_cap() {
     return v >= 1 ? (int64_t)v : INT64_MAX;
 }
 
-// Recognises the predicates pred_simple_kernel evaluates (see PredSimple): a symbolic run of the postfix program.
-bool compile_simple_predicate(const dq_predicate& pr, const dq_column* columns, int ncols, PredSimple& out) {
-    memset(&out, 0, sizeof(out));
-    enum { E_COL, E_CONST, E_BOOL };
-    struct Ent { int kind, idx; bool neg = false; };  // neg: a constant under unary minus (`x < -1`)
-    std::vector<Ent> st;
-    auto fixed_numeric = [&](int c) {
-        if (c < 0 || c >= ncols) return false;
-        switch (columns[c].spark_type) {
-            case DQ_TYPE_BOOLEAN: case DQ_TYPE_BYTE: case DQ_TYPE_SHORT: case DQ_TYPE_INT: case DQ_TYPE_DATE:
-            case DQ_TYPE_LONG: case DQ_TYPE_TIMESTAMP: case DQ_TYPE_FLOAT: case DQ_TYPE_DOUBLE: return true;
-            default: return false;
-        }
-    };
-    auto emit = [&](int b) {
-        if (out.nb >= kPredBCode) return false;
-        out.b[out.nb++] = (int8_t)b;
-        return true;
-    };
-    auto term = [&](int col, int op, int k, bool neg = false) -> int {  // k: constant index, or -1 for IS [NOT] NULL
-        if (out.nterms >= kPredTerms) return -1;
-        PredTerm& q = out.t[out.nterms];
-        q.col = col;
-        q.op = op;
-        if (k >= 0) {
-            const dq_const& c = pr.consts[k];
-            const int ty = columns[col].spark_type;
-            q.dbl = (ty == DQ_TYPE_FLOAT || ty == DQ_TYPE_DOUBLE || c.tag == DQ_V_DOUBLE) ? 1 : 0;
-            // Spark's UnaryMinus on a literal: a Long negates with wrap-around, a Double flips its sign
-            q.ci = neg ? (int64_t)(0ull - (uint64_t)c.i64) : c.i64;
-            q.cd = c.tag == DQ_V_DOUBLE ? (neg ? -c.f64 : c.f64) : (double)q.ci;
-        }
-        return out.nterms++;
-    };
-    auto flip = [](int op) {
-        switch (op) {
-            case DQ_P_LT: return (int)DQ_P_GT;
-            case DQ_P_LE: return (int)DQ_P_GE;
-            case DQ_P_GT: return (int)DQ_P_LT;
-            case DQ_P_GE: return (int)DQ_P_LE;
-            default: return op;
-        }
-    };
-    auto const_ok = [&](int k) {
-        if (k < 0 || k >= pr.n_consts) return false;
-        const int tag = pr.consts[k].tag;
-        return tag == DQ_V_BOOL || tag == DQ_V_LONG || tag == DQ_V_DOUBLE;
-    };
-    for (int pc = 0; pc + 1 < pr.code_len; pc += 2) {
-        const int op = pr.code[pc], arg = pr.code[pc + 1];
-        switch (op) {
-            case DQ_P_COL:
-                if (!fixed_numeric(arg)) return false;
-                st.push_back({E_COL, arg});
-                break;
-            case DQ_P_CONST:
-                if (!const_ok(arg)) return false;
-                st.push_back({E_CONST, arg});
-                break;
-            case DQ_P_EQ: case DQ_P_NE: case DQ_P_LT: case DQ_P_LE: case DQ_P_GT: case DQ_P_GE: {
-                if (st.size() < 2) return false;
-                const Ent b = st.back(); st.pop_back();
-                const Ent a = st.back(); st.pop_back();
-                int k;
-                if (a.kind == E_COL && b.kind == E_CONST) k = term(a.idx, op, b.idx, b.neg);
-                else if (a.kind == E_CONST && b.kind == E_COL) k = term(b.idx, flip(op), a.idx, a.neg);
-                else return false;
-                if (k < 0 || !emit(k)) return false;
-                st.push_back({E_BOOL, 0});
-                break;
-            }
-            case DQ_P_IS_NULL: case DQ_P_IS_NOT_NULL: {
-                if (st.empty() || st.back().kind != E_COL) return false;
-                const int k = term(st.back().idx, op, -1);
-                st.pop_back();
-                if (k < 0 || !emit(k)) return false;
-                st.push_back({E_BOOL, 0});
-                break;
-            }
-            case DQ_P_AND: case DQ_P_OR: {
-                if (st.size() < 2 || st[st.size() - 1].kind != E_BOOL || st[st.size() - 2].kind != E_BOOL) return false;
-                st.pop_back();
-                if (!emit(op == DQ_P_AND ? kPB_AND : kPB_OR)) return false;
-                break;
-            }
-            case DQ_P_NOT:
-                if (st.empty() || st.back().kind != E_BOOL || !emit(kPB_NOT)) return false;
-                break;
-            case DQ_P_NEG: {  // -constant (a LONG / DOUBLE literal): folded into the leaf's constant
-                if (st.empty() || st.back().kind != E_CONST) return false;
-                const int tag = pr.consts[st.back().idx].tag;
-                if (tag != DQ_V_LONG && tag != DQ_V_DOUBLE) return false;
-                st.back().neg = !st.back().neg;
-                break;
-            }
-            case DQ_P_IN: {  // x IN (c1..cn) with non-NULL constants == (x = c1) OR ... OR (x = cn)
-                const int n = arg;
-                if (n < 1 || (int)st.size() < n + 1) return false;
-                const size_t base = st.size() - n - 1;
-                if (st[base].kind != E_COL) return false;
-                for (int i = 0; i < n; ++i) {
-                    if (st[base + 1 + i].kind != E_CONST) return false;
-                    const int k = term(st[base].idx, DQ_P_EQ, st[base + 1 + i].idx, st[base + 1 + i].neg);
-                    if (k < 0 || !emit(k)) return false;
-                    if (i > 0 && !emit(kPB_OR)) return false;
-                }
-                st.resize(base);
-                st.push_back({E_BOOL, 0});
-                break;
-            }
-            default:
-                return false;
-        }
-        if (st.size() > 24) return false;
-    }
-    return st.size() == 1 && st[0].kind == E_BOOL && out.nterms > 0;
-}
-
 // Which kernel a launch group runs (mirrors values_kernel_for in scan.hip).
 int scan_kernel_family(int kind, int P, int nc, int heavy) {
     if (kind == SK_BITS) return DQ_KERNEL_BITS;
@@ -228,18 +107,6 @@ int ensure_side_streams(dq_ctx* ctx) {
     DQ_HIP(ctx, hipEventCreateWithFlags(&ctx->fork_ev, hipEventDisableTiming));
     return DQ_OK;
 }
-
-// Bump allocator over the context arena. Two passes: measure, then (after growth) assign.
-struct Bump {
-    size_t off = 0;
-    uint8_t* base = nullptr;
-    void* take(size_t bytes, size_t align = 256) {
-        off = align_up(off, align);
-        void* p = base ? base + off : nullptr;
-        off += bytes;
-        return p;
-    }
-};
 
 int ensure_arena(dq_ctx* ctx, size_t bytes) {
     if (bytes <= ctx->arena_cap) return DQ_OK;
@@ -272,16 +139,500 @@ int ensure_pinned(dq_ctx* ctx, size_t bytes) {
     return DQ_OK;
 }
 
-bool is_numeric_type(int t) {
-    // Preconditions.isNumeric (A/Analyzer.scala:329-343)
-    return t == DQ_TYPE_BYTE || t == DQ_TYPE_SHORT || t == DQ_TYPE_INT || t == DQ_TYPE_LONG ||
-           t == DQ_TYPE_FLOAT || t == DQ_TYPE_DOUBLE || t == DQ_TYPE_DECIMAL;
-}
-bool is_fixed_width(int t) { return elem_of(t) != ET_NONE; }
+// Pinned staging of one call's uploads and read-backs (the buffer is free: the caller synchronised the stream). The
+// callers size ctx->pinned from what they stage; a piece that does not fit fails the call instead of being written.
+struct Stager {
+    dq_ctx* ctx;
+    size_t off = 0;
+    void* take(size_t n) {
+        off = align_up(off, 16);
+        if (off + n > ctx->pinned_cap) return nullptr;
+        void* h = ctx->pinned + off;
+        off += n;
+        return h;
+    }
+    int upload(void* dst, const void* src, size_t n) {
+        if (!n) return DQ_OK;
+        void* h = take(n);
+        if (!h) return fail(ctx, DQ_ERR_DEVICE, "pinned staging of %zu bytes cannot hold %zu more", ctx->pinned_cap, n);
+        memcpy(h, src, n);
+        DQ_HIP(ctx, hipMemcpyAsync(dst, h, n, hipMemcpyHostToDevice, ctx->stream));
+        return DQ_OK;
+    }
+    // Queues the copy of n device bytes into staging; *h is readable once the stream is synchronised.
+    int download(void** h, const void* src, size_t n) {
+        *h = take(n);
+        if (!*h) return fail(ctx, DQ_ERR_DEVICE, "pinned staging of %zu bytes cannot hold %zu more", ctx->pinned_cap, n);
+        DQ_HIP(ctx, hipMemcpyAsync(*h, src, n, hipMemcpyDeviceToHost, ctx->stream));
+        return DQ_OK;
+    }
+};
 
-int64_t padded_words_for(int64_t nrows) {
-    const int64_t tiles = std::max<int64_t>(1, (nrows + kTileRows - 1) / kTileRows);
-    return tiles * (kTileRows / 64);
+// Staging bytes of one run_predicate.
+size_t pred_stage_bytes(const dq_predicate& pr) {
+    return align_up(sizeof(PredProgram), 16) + align_up(sizeof(int32_t) * (size_t)pr.code_len, 16) +
+           align_up(sizeof(dq_const) * (size_t)std::max(pr.n_consts, 0), 16) + align_up((size_t)std::max<int64_t>(pr.strings_len, 0), 16);
+}
+
+PredColumn pred_column(const dq_column& col, const void* values, const void* validity, const void* offsets) {
+    PredColumn pc;
+    memset(&pc, 0, sizeof(pc));
+    pc.values = values;
+    pc.validity = (const uint64_t*)validity;
+    pc.offsets = (const int32_t*)offsets;
+    pc.spark_type = col.spark_type;
+    pc.elem = elem_of(col.spark_type);
+    pc.decimal_scale = col.decimal_scale;
+    return pc;
+}
+
+// Device addresses of one predicate's program pieces (the arena layout in dq_scan, ScratchBuffers in dq_dict_scan).
+struct PredDevice {
+    void *prog, *code, *consts, *strings;
+};
+
+// Upload and dispatch of one validated predicate over `columns` (pcols_dev: their PredColumn records on the device,
+// pc: the same on the host) into TRUE / NOT-NULL bitmaps of `pwords` words: PatternMatch, the simple-predicate kernel
+// or the general VM. *status (device, zeroed) is set by a row the device cannot evaluate (regex backtracking budget,
+// inexact string -> double); *may_set_status tells whether this predicate can do that.
+int run_predicate(dq_ctx* ctx, Stager& up, const dq_predicate& pr, const dq_column* columns, int ncols, const PredColumn* pc,
+                  const PredColumn* pcols_dev, const PredDevice& d, int64_t nrows, int64_t pwords, uint64_t* pt, uint64_t* pn,
+                  int32_t* status, bool vm_forced, bool* may_set_status) {
+    int rc = up.upload(d.code, pr.code, sizeof(int32_t) * (size_t)pr.code_len);
+    if (rc) return rc;
+    if (pr.n_consts > 0 && (rc = up.upload(d.consts, pr.consts, sizeof(dq_const) * (size_t)pr.n_consts))) return rc;
+    if (pr.strings_len > 0 && (rc = up.upload(d.strings, pr.strings, (size_t)pr.strings_len))) return rc;
+    PredProgram pg;
+    pg.code = (const int32_t*)d.code;
+    pg.consts = (const dq_const*)d.consts;
+    pg.strings = (const uint8_t*)d.strings;
+    pg.code_len = pr.code_len;
+    pg.n_consts = pr.n_consts;
+    if ((rc = up.upload(d.prog, &pg, sizeof(pg)))) return rc;
+    if (pr.code_len == 4 && pr.code[2] == DQ_P_REGEX) {
+        const dq_const& k = pr.consts[pr.code[3]];
+        launch_regex(pc[pr.code[1]], (const int32_t*)((const uint8_t*)d.strings + k.str_offset), nrows, pwords, pt, pn, status,
+                     ctx->stream);
+        ctx->kernel_launches[DQ_KERNEL_REGEX]++;
+        *may_set_status = true;
+    } else if (PredSimple ps; !vm_forced && compile_simple_predicate(pr, columns, ncols, ps)) {
+        launch_pred_simple(ps, pcols_dev, nrows, pwords, pt, pn, ctx->stream);
+        ctx->kernel_launches[DQ_KERNEL_PRED_SIMPLE]++;
+        *may_set_status = false;
+    } else {
+        // rx: the program holds RLIKE; str: it has a string operand, which a comparison, arithmetic or CAST may have to
+        // convert to DOUBLE (a conversion the device cannot round exactly sets status)
+        bool rx = false, str = false;
+        for (int k = 0; k + 1 < pr.code_len; k += 2) {
+            const int a = pr.code[k + 1];
+            rx |= pr.code[k] == DQ_P_RLIKE;
+            str |= pr.code[k] == DQ_P_COL && a >= 0 && a < ncols && columns[a].spark_type == DQ_TYPE_STRING;
+            str |= pr.code[k] == DQ_P_CONST && a >= 0 && a < pr.n_consts && pr.consts[a].tag == DQ_V_STRING;
+        }
+        launch_predicate((const PredProgram*)d.prog, rx, status, pcols_dev, nrows, pwords, pt, pn, ctx->stream);
+        ctx->kernel_launches[DQ_KERNEL_PRED_VM]++;
+        *may_set_status = rx || str;
+    }
+    DQ_HIP(ctx, hipGetLastError());
+    return DQ_OK;
+}
+
+// One dq_scan call on a single device: its arguments, its plan (scan_plan.h) and, once the arena is sized, the device
+// addresses the plan's indices resolve to.
+struct ScanCall {
+    dq_ctx* ctx;
+    const dq_column* columns;
+    int ncols;
+    int64_t nrows;
+    const dq_op* ops;
+    int nops;
+    const dq_predicate* preds;
+    int npreds;
+    ScanOptions options;
+    ScanUse use;
+    ScanPlan plan;
+    ScanGeometry geo;
+    ScanLayout L;
+    bool concurrent = false;
+    std::vector<const void*> val, valid, offs;  // per column: device values / validity / string offsets
+    std::vector<PredColumn> pc;                 // per column, host copy of the records at L.pcols
+    bool any_status = false;                    // some predicate may set its status word: read the words back
+
+    template <class T>
+    T* at(size_t off) const { return off == kNoOffset ? nullptr : (T*)(ctx->arena + off); }
+    uint64_t* pred_t(int p) const { return p >= 0 ? at<uint64_t>(L.pred[p].t) : nullptr; }
+    uint64_t* pred_nn(int p) const { return p >= 0 ? at<uint64_t>(L.pred[p].nn) : nullptr; }
+    uint64_t* mask(int p, int m) const { return (uint64_t*)(ctx->arena + L.pred[p].mask0 + (size_t)m * L.mask_stride); }
+    int64_t pwords() const { return padded_words_for(nrows); }
+};
+
+// ---- resolve: plan record + device addresses -> device descriptor ---------------------------------------------------
+SlotDesc resolve_slot(const ScanCall& sc, const PlanSlot& sl) {
+    SlotDesc sd;
+    memset(&sd, 0, sizeof(sd));
+    sd.kind = sl.kind;
+    sd.ncols = 1;
+    sd.rows_per_load = 8;
+    sd.col[0].hll_slot = sd.col[1].hll_slot = -1;
+    sd.col[1].elem = ET_NONE;
+    sd.where_t = sc.pred_t(sl.where);
+    sd.where_nn = sc.pred_nn(sl.where);
+    if (sl.kind == SK_VALUES) {
+        sd.ncols = sl.ncols;
+        sd.corr = sl.corr;
+        sd.rows_per_load = sl.rows_per_load;
+        for (int k = 0; k < sl.ncols; ++k) {
+            const PlanCol& c = sl.col[k];
+            ColDesc& cd = sd.col[k];
+            cd.values = sc.val[c.column];
+            // a consumer of a masked filter reads its mask, valid & where TRUE, in place of its validity
+            cd.validity = c.mask_pred >= 0 ? sc.mask(c.mask_pred, c.mask_index) : (const uint64_t*)sc.valid[c.column];
+            cd.spark_type = sc.columns[c.column].spark_type;
+            cd.elem = c.elem;
+            cd.flags = c.flags;
+            cd.hll_slot = c.hll_slot;
+            cd.pred_op = c.pred_op;
+            cd.pred_kind = c.pred_kind;
+            cd.pred_i = c.pred_i;
+            cd.pred_d = c.pred_d;
+        }
+        sd.wout = sl.producer_of >= 0 ? sc.at<WhereOut>(sc.L.pred[sl.producer_of].wout) : nullptr;
+    } else if (sl.kind == SK_BITS) {
+        if (sl.tag == BT_COMPLETENESS) sd.bits_valid = (const uint64_t*)sc.valid[sl.ref];
+        if (sl.tag == BT_COMPLIANCE) {
+            sd.pred_t = sc.pred_t(sl.ref);
+            sd.pred_nn = sc.pred_nn(sl.ref);
+        }
+    }
+    return sd;
+}
+
+StrSlot resolve_str_slot(const ScanCall& sc, const PlanStrSlot& ps) {
+    StrSlot ss;
+    memset(&ss, 0, sizeof(ss));
+    ss.data = (const uint8_t*)sc.val[ps.column];
+    ss.offsets = (const int32_t*)sc.offs[ps.column];
+    ss.values = sc.val[ps.column];
+    ss.validity = (const uint64_t*)sc.valid[ps.column];
+    ss.where_t = sc.pred_t(ps.where);
+    ss.spark_type = sc.columns[ps.column].spark_type;
+    ss.decimal_scale = sc.columns[ps.column].decimal_scale;
+    ss.flags = ps.flags;
+    ss.hll_slot = ps.hll_slot;
+    return ss;
+}
+
+D128Slot resolve_d128_slot(const ScanCall& sc, const PlanD128Slot& pd) {
+    D128Slot ds;
+    memset(&ds, 0, sizeof(ds));
+    ds.values = sc.val[pd.column];
+    ds.validity = (const uint64_t*)sc.valid[pd.column];
+    ds.where_t = sc.pred_t(pd.where);
+    ds.where_nn = sc.pred_nn(pd.where);
+    ds.flags = pd.flags;
+    ds.hll_slot = pd.hll_slot;
+    ds.scale = sc.columns[pd.column].decimal_scale;
+    return ds;
+}
+
+WhereOut resolve_where_out(const ScanCall& sc, int p) {
+    const WherePlan& wp = sc.plan.where[p];
+    WhereOut wo;
+    memset(&wo, 0, sizeof(wo));
+    wo.prog = wp.prog;
+    wo.nmasks = (int)wp.mask_col.size();
+    wo.bitmaps = wp.bitmaps ? 1 : 0;
+    wo.where_t = sc.pred_t(p);
+    wo.where_nn = sc.pred_nn(p);
+    for (int m = 0; m < wo.nmasks; ++m) {
+        wo.valid[m] = (const uint64_t*)sc.valid[wp.mask_col[m]];
+        wo.mask[m] = sc.mask(p, m);
+    }
+    return wo;
+}
+
+// ---- the stages of dq_scan, in call order -----------------------------------------------------------------------------
+// A multi-device context: host columns are row-sharded over the devices (multi.cpp).
+int scan_multi_device(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, const dq_op* ops, int nops,
+                      const dq_predicate* preds, int npreds, dq_state* out, uint32_t flags) {
+    if (flags & DQ_SCAN_OUT_DEVICE)
+        return fail(ctx, DQ_ERR_UNSUPPORTED, "a multi-device context returns host states (no DQ_SCAN_OUT_DEVICE)");
+    for (int c = 0; c < ncols; ++c) {
+        if (columns[c].spark_type == DQ_TYPE_DECIMAL128)
+            return fail(ctx, DQ_ERR_UNSUPPORTED, "column %d: DECIMAL128 columns need a single-device context", c);
+        if (columns[c].flags & DQ_COL_DEVICE)
+            return fail(ctx, DQ_ERR_UNSUPPORTED, "device columns of a multi-device context go through dq_scan_sharded");
+        if (columns[c].length != nrows)
+            return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "column %d has %lld rows, batch has %lld", c,
+                        (long long)columns[c].length, (long long)nrows);
+    }
+    const int n = (int)ctx->subs.size();
+    std::vector<std::vector<dq_column>> cols(n, std::vector<dq_column>(std::max(ncols, 1)));
+    std::vector<std::vector<std::vector<int32_t>>> scratch(n);
+    std::vector<const dq_column*> ptrs(n);
+    std::vector<int64_t> rows(n);
+    for (int i = 0; i < n; ++i) {
+        int64_t r0 = 0;
+        shard_bounds(nrows, n, i, &r0, &rows[i]);
+        shard_columns(columns, ncols, r0, rows[i], cols[i].data(), scratch[i]);
+        ptrs[i] = cols[i].data();
+    }
+    return multi_scan(ctx, ptrs.data(), rows.data(), ncols, ops, nops, preds, npreds, out);
+}
+
+// Grids of the plan's launches: occupancy per shape (cached on the context), the chip shared between concurrent launches.
+int scan_geometry(ScanCall& sc) {
+    dq_ctx* ctx = sc.ctx;
+    std::vector<int> occ;
+    occ.reserve(sc.plan.groups.size());
+    for (const PlanGroup& g : sc.plan.groups) {
+        auto oc = ctx->occupancy.find(g.key);
+        if (oc == ctx->occupancy.end())
+            oc = ctx->occupancy.emplace(g.key, std::max(1, scan_group_blocks_per_cu(g.kind, g.P, g.nc, g.f0, g.f1, g.heavy))).first;
+        occ.push_back(oc->second);
+    }
+    sc.concurrent = scan_concurrency() && sc.plan.nlaunch() > 1 && ensure_side_streams(ctx) == DQ_OK;
+    const int sgrid = sc.plan.sslots.empty() ? 0 : string_scan_grid(ctx->cus, sc.nrows);
+    const int dgrid = sc.plan.dslots.empty() ? 0 : decimal128_scan_grid(ctx->cus, sc.nrows);
+    sc.geo = plan_geometry(sc.plan, ctx->cus, (sc.nrows + kTileRows - 1) / kTileRows, scan_grid_cap(), sc.concurrent, sgrid,
+                           dgrid, occ.data());
+    return DQ_OK;
+}
+
+// Host columns are copied into the arena; device columns are read in place.
+int stage_columns(ScanCall& sc) {
+    dq_ctx* ctx = sc.ctx;
+    const size_t bitmap_bytes = (size_t)(sc.nrows + 7) / 8;
+    sc.val.assign(sc.ncols, nullptr);
+    sc.valid.assign(sc.ncols, nullptr);
+    sc.offs.assign(sc.ncols, nullptr);
+    for (int c = 0; c < sc.ncols; ++c) {
+        const dq_column& col = sc.columns[c];
+        if (!sc.use.col_used[c]) continue;
+        if (col.flags & DQ_COL_DEVICE) {
+            sc.val[c] = col.values;
+            sc.valid[c] = col.validity;
+            sc.offs[c] = col.offsets;
+            continue;
+        }
+        const ScanLayout::Column& lc = sc.L.col[c];
+        void* v = sc.at<void>(lc.values);
+        void* vd = sc.at<void>(lc.validity);
+        void* od = sc.at<void>(lc.offsets);
+        if (lc.vbytes) DQ_HIP(ctx, hipMemcpyAsync(v, col.values, lc.vbytes, hipMemcpyHostToDevice, ctx->stream));
+        if (vd && bitmap_bytes) DQ_HIP(ctx, hipMemcpyAsync(vd, col.validity, bitmap_bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (od) DQ_HIP(ctx, hipMemcpyAsync(od, col.offsets, ((size_t)sc.nrows + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+        sc.val[c] = v;
+        sc.valid[c] = vd;
+        sc.offs[c] = od;
+    }
+    return DQ_OK;
+}
+
+// The predicate passes (bitmaps of unmasked `where` filters and Compliance predicates), then the masked filters'
+// descriptors and their standalone producers: all before the first scan launch.
+int run_predicates(ScanCall& sc, Stager& up) {
+    dq_ctx* ctx = sc.ctx;
+    const ScanPlan& plan = sc.plan;
+    int32_t* status = sc.at<int32_t>(sc.L.status);
+    const PredColumn* pcols = sc.at<PredColumn>(sc.L.pcols);
+    int npred_pass = 0;
+    for (int p = 0; p < sc.npreds; ++p) npred_pass += plan.pred_pass[p];
+    if (npred_pass || plan.nstandalone) {
+        DQ_HIP(ctx, hipMemsetAsync(status, 0, sizeof(int32_t) * std::max(sc.npreds, 1), ctx->stream));
+        sc.pc.resize(std::max(sc.ncols, 1));
+        memset(sc.pc.data(), 0, sizeof(PredColumn) * sc.pc.size());
+        for (int c = 0; c < sc.ncols; ++c) sc.pc[c] = pred_column(sc.columns[c], sc.val[c], sc.valid[c], sc.offs[c]);
+        int rc = up.upload((void*)pcols, sc.pc.data(), sizeof(PredColumn) * sc.pc.size());
+        if (rc) return rc;
+        for (int p = 0; p < sc.npreds; ++p) {
+            if (!plan.pred_pass[p]) continue;
+            const PredOffsets& po = sc.L.pred[p];
+            const PredDevice d{sc.at<void>(po.prog), sc.at<void>(po.code), sc.at<void>(po.consts), sc.at<void>(po.strings)};
+            bool may = false;
+            rc = run_predicate(ctx, up, sc.preds[p], sc.columns, sc.ncols, sc.pc.data(), pcols, d, sc.nrows, sc.pwords(),
+                               sc.pred_t(p), sc.pred_nn(p), status + p, sc.options.pred_vm, &may);
+            if (rc) return rc;
+            sc.any_status |= may;
+        }
+    }
+    for (int p = 0; p < sc.npreds; ++p) {
+        const WherePlan& wp = plan.where[p];
+        if (!wp.masked) continue;
+        const WhereOut wo = resolve_where_out(sc, p);
+        WhereOut* wodev = sc.at<WhereOut>(sc.L.pred[p].wout);
+        const int rc = up.upload(wodev, &wo, sizeof(wo));
+        if (rc) return rc;
+        if (wp.producer < 0) {
+            launch_where_masks(wodev, wp.prog, pcols, sc.nrows, sc.pwords(), sc.at<SlotPartial>(sc.L.partials), wp.wslot,
+                               sc.geo.gstride, sc.geo.slot_nblocks[wp.wslot], ctx->stream);
+            DQ_HIP(ctx, hipGetLastError());
+            ctx->kernel_launches[DQ_KERNEL_WHERE_MASKS]++;
+        }
+    }
+    return DQ_OK;
+}
+
+// Slot descriptors, op maps, launch order and block counts of the value / bits / string launches.
+int upload_descriptors(ScanCall& sc, Stager& up) {
+    const ScanPlan& plan = sc.plan;
+    const int nslots = (int)plan.slots.size();
+    std::vector<SlotDesc> slots;
+    slots.reserve(nslots);
+    for (const PlanSlot& sl : plan.slots) slots.push_back(resolve_slot(sc, sl));
+    int rc = up.upload(sc.at<void>(sc.L.slots), slots.data(), sizeof(SlotDesc) * nslots);
+    if (rc) return rc;
+    if ((rc = up.upload(sc.at<void>(sc.L.ops), plan.opmap.data(), sizeof(OpMap) * sc.nops))) return rc;
+    if (nslots) {
+        std::vector<int32_t> order;
+        order.reserve(nslots);
+        for (const PlanGroup& g : plan.groups) order.insert(order.end(), g.slots.begin(), g.slots.end());
+        if ((rc = up.upload(sc.at<void>(sc.L.order), order.data(), sizeof(int32_t) * order.size()))) return rc;
+        rc = up.upload(sc.at<void>(sc.L.slot_nblocks), sc.geo.slot_nblocks.data(), sizeof(int32_t) * sc.geo.slot_nblocks.size());
+        if (rc) return rc;
+    }
+    std::vector<StrSlot> sslots;
+    sslots.reserve(plan.sslots.size());
+    for (const PlanStrSlot& ps : plan.sslots) sslots.push_back(resolve_str_slot(sc, ps));
+    return up.upload(sc.at<void>(sc.L.sslots), sslots.data(), sizeof(StrSlot) * sslots.size());
+}
+
+// The scan launches: fused `where` producers first on the ctx stream (every other launch reads their masks), then the
+// other groups and the string scan in order on the ctx stream, or one stream each (fork / join) when concurrent; the
+// decimal128 launch after the join.
+int launch_scans(ScanCall& sc, Stager& up) {
+    dq_ctx* ctx = sc.ctx;
+    const ScanPlan& plan = sc.plan;
+    const ScanGeometry& geo = sc.geo;
+    const int nsslots = (int)plan.sslots.size(), ndslots = (int)plan.dslots.size();
+    const SlotDesc* dslots = sc.at<SlotDesc>(sc.L.slots);
+    const int32_t* order = sc.at<int32_t>(sc.L.order);
+    SlotPartial* partials = sc.at<SlotPartial>(sc.L.partials);
+    uint8_t* hllp = sc.at<uint8_t>(sc.L.hll_partials);
+    int used_side = 0;
+    auto launch_stream = [&](int i) -> hipStream_t {
+        if (!sc.concurrent || i == 0) return ctx->stream;
+        const int j = (i - 1) % dq_ctx::kSide;
+        used_side = std::max(used_side, j + 1);
+        return ctx->side[j];
+    };
+    int li = 0;
+    size_t goff = 0, gi = 0;
+    auto launch_group = [&](size_t i, hipStream_t st) -> int {
+        const PlanGroup& g = plan.groups[i];
+        if (launch_scan_group(g.kind, g.P, g.nc, g.f0, g.f1, g.heavy, dslots, order + goff, (int)g.slots.size(), sc.nrows,
+                              geo.ntiles, geo.gstride, geo.grid[i], partials, hllp, st) != 0)
+            return fail(ctx, DQ_ERR_DEVICE, "scan launch failed for shape (%d,%d,%d)", g.kind, g.P, g.nc);
+        DQ_HIP(ctx, hipGetLastError());
+        ctx->kernel_launches[scan_kernel_family(g.kind, g.P, g.nc, g.heavy)]++;
+        goff += g.slots.size();
+        return DQ_OK;
+    };
+    int rc;
+    for (; gi < plan.groups.size() && plan.groups[gi].heavy == 3; ++gi)
+        if ((rc = launch_group(gi, ctx->stream))) return rc;
+    if (sc.concurrent) {
+        DQ_HIP(ctx, hipEventRecord(ctx->fork_ev, ctx->stream));
+        for (int j = 0; j < std::min(plan.nlaunch() - 1, dq_ctx::kSide); ++j)
+            DQ_HIP(ctx, hipStreamWaitEvent(ctx->side[j], ctx->fork_ev, 0));
+    }
+    for (; gi < plan.groups.size(); ++gi)
+        if ((rc = launch_group(gi, launch_stream(li++)))) return rc;
+    if (nsslots) {
+        launch_string_scan(sc.at<StrSlot>(sc.L.sslots), nsslots, sc.nrows, geo.sgrid, geo.gstride, sc.at<StrPartial>(sc.L.spartials),
+                           hllp, launch_stream(li++));
+        DQ_HIP(ctx, hipGetLastError());
+        ctx->kernel_launches[DQ_KERNEL_STRINGS]++;
+    }
+    for (int j = 0; j < used_side; ++j) {
+        DQ_HIP(ctx, hipEventRecord(ctx->join_ev[j], ctx->side[j]));
+        DQ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->join_ev[j], 0));
+    }
+    if (ndslots) {
+        std::vector<D128Slot> ds;
+        ds.reserve(ndslots);
+        for (const PlanD128Slot& pd : plan.dslots) ds.push_back(resolve_d128_slot(sc, pd));
+        if ((rc = up.upload(sc.at<void>(sc.L.dslots), ds.data(), sizeof(D128Slot) * ndslots))) return rc;
+        launch_decimal128_scan(sc.at<D128Slot>(sc.L.dslots), ndslots, sc.nrows, geo.dgrid, geo.gstride,
+                               sc.at<D128Partial>(sc.L.dpartials), hllp, ctx->stream);
+        DQ_HIP(ctx, hipGetLastError());
+        ctx->kernel_launches[DQ_KERNEL_DECIMAL128]++;
+    }
+    return DQ_OK;
+}
+
+// Per-block partials -> final slot partials and HLL registers -> one dq_state per op at `dout`.
+int reduce_and_finalize(ScanCall& sc, Stager& up, dq_state* dout) {
+    dq_ctx* ctx = sc.ctx;
+    const ScanPlan& plan = sc.plan;
+    const ScanGeometry& geo = sc.geo;
+    const int nslots = (int)plan.slots.size(), nsslots = (int)plan.sslots.size(), ndslots = (int)plan.dslots.size();
+    SlotPartial* finals = sc.at<SlotPartial>(sc.L.finals);
+    uint8_t* hllf = sc.at<uint8_t>(sc.L.hll_final);
+    int rc;
+    if (nslots) {
+        launch_reduce_partials(sc.at<SlotPartial>(sc.L.partials), sc.at<int32_t>(sc.L.slot_nblocks), nslots, geo.gstride, finals,
+                               ctx->stream);
+        DQ_HIP(ctx, hipGetLastError());
+    }
+    if (nslots || nsslots || ndslots) ctx->scan_launches++;
+    if (plan.nhll) {
+        int32_t* dhll_nb = sc.at<int32_t>(sc.L.hll_nblocks);
+        if ((rc = up.upload(dhll_nb, geo.hll_nblocks.data(), sizeof(int32_t) * geo.hll_nblocks.size()))) return rc;
+        launch_reduce_hll(sc.at<uint8_t>(sc.L.hll_partials), dhll_nb, plan.nhll, geo.gstride, hllf, ctx->stream);
+        DQ_HIP(ctx, hipGetLastError());
+    }
+    launch_finalize(sc.at<OpMap>(sc.L.ops), sc.nops, finals, hllf, dout, ctx->stream);
+    DQ_HIP(ctx, hipGetLastError());
+    if (!plan.sopmap.empty()) {
+        StrOpMap* dsops = sc.at<StrOpMap>(sc.L.sops);
+        if ((rc = up.upload(dsops, plan.sopmap.data(), sizeof(StrOpMap) * plan.sopmap.size()))) return rc;
+        launch_finalize_strings(dsops, (int)plan.sopmap.size(), sc.at<StrPartial>(sc.L.spartials), geo.sgrid, geo.gstride, sc.nrows,
+                                dout, ctx->stream);
+        DQ_HIP(ctx, hipGetLastError());
+    }
+    if (!plan.dopmap.empty()) {
+        D128OpMap* ddops = sc.at<D128OpMap>(sc.L.dops);
+        if ((rc = up.upload(ddops, plan.dopmap.data(), sizeof(D128OpMap) * plan.dopmap.size()))) return rc;
+        launch_finalize_decimal128(sc.at<D128Slot>(sc.L.dslots), ndslots, ddops, (int)plan.dopmap.size(),
+                                   sc.at<D128Partial>(sc.L.dpartials), geo.dgrid, geo.gstride, sc.nrows, dout, ctx->stream);
+        DQ_HIP(ctx, hipGetLastError());
+    }
+    return DQ_OK;
+}
+
+// The predicates' status words (read only when one may be set), then the states: to `out`, or left at `out` on the
+// device (DQ_SCAN_OUT_DEVICE), where staged host columns must outlive the kernels.
+int read_back(ScanCall& sc, Stager& up, const dq_state* dout, dq_state* out, uint32_t flags) {
+    dq_ctx* ctx = sc.ctx;
+    int rc;
+    if (sc.any_status) {
+        // a row that exhausted the backtracking budget, or whose string the device cannot convert to DOUBLE exactly,
+        // fails the batch (never a silent count)
+        void* h = nullptr;
+        if ((rc = up.download(&h, sc.at<int32_t>(sc.L.status), sizeof(int32_t) * std::max(sc.npreds, 1)))) return rc;
+        DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const int32_t* hs = (const int32_t*)h;
+        for (int p = 0; p < sc.npreds; ++p)
+            if (sc.plan.pred_pass[p] && (hs[p] & 1))
+                return fail(ctx, DQ_ERR_UNSUPPORTED, "predicate %d: regex backtracking limit exceeded", p);
+        for (int p = 0; p < sc.npreds; ++p)
+            if (sc.plan.pred_pass[p] && hs[p])
+                return fail(ctx, DQ_ERR_UNSUPPORTED,
+                            "predicate %d: a string needs Double.parseDouble's arbitrary-precision path "
+                            "(hexadecimal literal, or > 19 significant digits on a rounding boundary)", p);
+    }
+    if (!(flags & DQ_SCAN_OUT_DEVICE)) {
+        void* h = nullptr;
+        if ((rc = up.download(&h, dout, sizeof(dq_state) * sc.nops))) return rc;
+        DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        memcpy(out, h, sizeof(dq_state) * sc.nops);
+    } else {
+        bool staged = false;
+        for (int c = 0; c < sc.ncols; ++c) staged |= sc.use.col_used[c] && !(sc.columns[c].flags & DQ_COL_DEVICE);
+        if (staged) DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return DQ_OK;
 }
 
 }  // namespace
@@ -553,1036 +904,38 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
     if (nops < 0 || ncols < 0 || npreds < 0 || nrows < 0 || (nops > 0 && (!ops || !out)))
         return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "invalid arguments");
     if (nops == 0) return DQ_OK;
-    if (!ctx->subs.empty()) {
-        // multi-device context: host columns are row-sharded over the devices (multi.cpp)
-        if (flags & DQ_SCAN_OUT_DEVICE)
-            return fail(ctx, DQ_ERR_UNSUPPORTED, "a multi-device context returns host states (no DQ_SCAN_OUT_DEVICE)");
-        for (int c = 0; c < ncols; ++c) {
-            if (columns[c].spark_type == DQ_TYPE_DECIMAL128)
-                return fail(ctx, DQ_ERR_UNSUPPORTED, "column %d: DECIMAL128 columns need a single-device context", c);
-            if (columns[c].flags & DQ_COL_DEVICE)
-                return fail(ctx, DQ_ERR_UNSUPPORTED, "device columns of a multi-device context go through dq_scan_sharded");
-            if (columns[c].length != nrows)
-                return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "column %d has %lld rows, batch has %lld", c,
-                            (long long)columns[c].length, (long long)nrows);
-        }
-        const int n = (int)ctx->subs.size();
-        std::vector<std::vector<dq_column>> cols(n, std::vector<dq_column>(std::max(ncols, 1)));
-        std::vector<std::vector<std::vector<int32_t>>> scratch(n);
-        std::vector<const dq_column*> ptrs(n);
-        std::vector<int64_t> rows(n);
-        for (int i = 0; i < n; ++i) {
-            int64_t r0 = 0;
-            shard_bounds(nrows, n, i, &r0, &rows[i]);
-            shard_columns(columns, ncols, r0, rows[i], cols[i].data(), scratch[i]);
-            ptrs[i] = cols[i].data();
-        }
-        return multi_scan(ctx, ptrs.data(), rows.data(), ncols, ops, nops, preds, npreds, out);
-    }
+    if (!ctx->subs.empty()) return scan_multi_device(ctx, columns, ncols, nrows, ops, nops, preds, npreds, out, flags);
     DQ_HIP(ctx, hipSetDevice(ctx->device));
 
-    // ---- validation ---------------------------------------------------------------------------
-    for (int c = 0; c < ncols; ++c) {
-        const dq_column& col = columns[c];
-        if (col.length != nrows)
-            return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "column %d has %lld rows, batch has %lld", c,
-                        (long long)col.length, (long long)nrows);
-        if (col.spark_type < DQ_TYPE_BOOLEAN || col.spark_type > DQ_TYPE_DECIMAL128)
-            return fail(ctx, DQ_ERR_UNSUPPORTED, "column %d: unknown spark type %d", c, col.spark_type);
-        const bool wide = col.spark_type == DQ_TYPE_DECIMAL128;
-        if (wide && (col.decimal_precision < 19 || col.decimal_precision > 38 || col.decimal_scale < 0 ||
-                     col.decimal_scale > col.decimal_precision))
-            return fail(ctx, DQ_ERR_UNSUPPORTED, "column %d: DECIMAL128 needs 19 <= precision <= 38 and 0 <= scale <= precision", c);
-        if (col.spark_type == DQ_TYPE_STRING && nrows > 0 && !col.offsets)
-            return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "string column %d without offsets", c);
-        if (col.flags & DQ_COL_OFFSETS64)
-            return fail(ctx, DQ_ERR_UNSUPPORTED, "column %d: int64 string offsets are for the grouping builds only", c);
-        if (col.spark_type == DQ_TYPE_DECIMAL && (col.decimal_precision > 18 || col.decimal_scale < 0 || col.decimal_scale > 18))
-            return fail(ctx, DQ_ERR_UNSUPPORTED, "column %d: decimal precision > 18 unsupported", c);
-        if ((col.flags & DQ_COL_DEVICE) && nrows > 0) {
-            const int e = elem_of(col.spark_type);
-            // strings: 4-byte aligned UTF-8 (read as dwords), padded by 16 bytes past offsets[length]
-            const size_t va = wide ? 16 : (e == ET_NONE ? 4 : (elem_size(e) == 1 ? 8 : 16));
-            if (((uintptr_t)col.values % va) != 0 || ((uintptr_t)col.validity % 8) != 0)
-                return fail(ctx, DQ_ERR_ALIGNMENT, "device column %d: values must be %zu-byte and validity 8-byte aligned", c, va);
-        }
-    }
-    auto col_ok = [&](int c) { return c >= 0 && c < ncols; };
-    std::vector<char> pred_used(npreds, 0);
-    std::vector<char> col_used(ncols, 0);
-    // ops over a DECIMAL128 column: answered by the decimal128 launch, never by a value / bits / string slot
-    std::vector<char> wide_op(nops, 0);
-    for (int i = 0; i < nops; ++i) {
-        const dq_op& op = ops[i];
-        if (op.where >= npreds || op.where < -1) return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "op %d: bad where index", i);
-        if (op.where >= 0) pred_used[op.where] = 1;
-        if (op.kind != DQ_OP_SIZE && op.kind != DQ_OP_COMPLIANCE) {
-            const bool w0 = col_ok(op.column[0]) && columns[op.column[0]].spark_type == DQ_TYPE_DECIMAL128;
-            const bool w1 = op.kind == DQ_OP_CORRELATION && col_ok(op.column[1]) &&
-                            columns[op.column[1]].spark_type == DQ_TYPE_DECIMAL128;
-            if (w0 || w1) {
-                const bool ok = op.kind == DQ_OP_COMPLETENESS || op.kind == DQ_OP_MEAN || op.kind == DQ_OP_SUM ||
-                                op.kind == DQ_OP_MINIMUM || op.kind == DQ_OP_MAXIMUM ||
-                                op.kind == DQ_OP_STANDARD_DEVIATION || op.kind == DQ_OP_APPROX_COUNT_DISTINCT;
-                if (!ok) return fail(ctx, DQ_ERR_UNSUPPORTED, "op %d: kind %d is not supported over a DECIMAL128 column", i, op.kind);
-                wide_op[i] = 1;
-                col_used[op.column[0]] = 1;
-                continue;
-            }
-        }
-        switch (op.kind) {
-            case DQ_OP_SIZE: break;
-            case DQ_OP_COMPLIANCE:
-                if (op.predicate < 0 || op.predicate >= npreds)
-                    return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "op %d: Compliance needs a predicate", i);
-                pred_used[op.predicate] = 1;
-                break;
-            case DQ_OP_COMPLETENESS:
-                if (!col_ok(op.column[0])) return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "op %d: bad column", i);
-                col_used[op.column[0]] = 1;
-                break;
-            case DQ_OP_MEAN: case DQ_OP_SUM: case DQ_OP_MINIMUM: case DQ_OP_MAXIMUM: case DQ_OP_STANDARD_DEVIATION:
-                if (!col_ok(op.column[0])) return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "op %d: bad column", i);
-                if (!is_numeric_type(columns[op.column[0]].spark_type))
-                    return fail(ctx, DQ_ERR_UNSUPPORTED, "op %d: column %d is not numeric", i, op.column[0]);
-                col_used[op.column[0]] = 1;
-                break;
-            case DQ_OP_CORRELATION:
-                if (!col_ok(op.column[0]) || !col_ok(op.column[1]))
-                    return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "op %d: bad column", i);
-                if (!is_numeric_type(columns[op.column[0]].spark_type) || !is_numeric_type(columns[op.column[1]].spark_type))
-                    return fail(ctx, DQ_ERR_UNSUPPORTED, "op %d: correlation needs numeric columns", i);
-                col_used[op.column[0]] = col_used[op.column[1]] = 1;
-                break;
-            case DQ_OP_APPROX_COUNT_DISTINCT:
-            case DQ_OP_DATATYPE:
-                if (!col_ok(op.column[0])) return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "op %d: bad column", i);
-                col_used[op.column[0]] = 1;
-                break;
-            case DQ_OP_MIN_LENGTH: case DQ_OP_MAX_LENGTH:
-                if (!col_ok(op.column[0])) return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "op %d: bad column", i);
-                if (columns[op.column[0]].spark_type != DQ_TYPE_STRING)
-                    return fail(ctx, DQ_ERR_UNSUPPORTED, "op %d: MinLength/MaxLength need a string column", i);
-                col_used[op.column[0]] = 1;
-                break;
-            default:
-                return fail(ctx, DQ_ERR_UNSUPPORTED, "op %d: kind %d not implemented by the fused scan", i, op.kind);
-        }
-    }
-    for (int p = 0; p < npreds; ++p) {
-        if (!pred_used[p]) continue;
-        const dq_predicate& pr = preds[p];
-        if (pr.code_len <= 0 || (pr.code_len & 1) || !pr.code)
-            return fail(ctx, DQ_ERR_PREDICATE, "predicate %d: empty or odd-length program", p);
-        if (pr.code_len == 4 && pr.code[2] == DQ_P_REGEX) {
-            const int c = pr.code[1], k = pr.code[3];
-            if (pr.code[0] != DQ_P_COL || !col_ok(c) || k < 0 || k >= pr.n_consts || pr.consts[k].tag != DQ_V_STRING ||
-                pr.consts[k].str_offset < 0 || (pr.consts[k].str_offset & 3) ||
-                pr.consts[k].str_offset + pr.consts[k].str_len > pr.strings_len ||
-                !dq::rx::rx_image_ok(pr.strings + pr.consts[k].str_offset, pr.consts[k].str_len))
-                return fail(ctx, DQ_ERR_PREDICATE, "predicate %d: malformed REGEX program", p);
-            const int t = columns[c].spark_type;
-            if (t < DQ_TYPE_BOOLEAN || t > DQ_TYPE_DECIMAL)
-                return fail(ctx, DQ_ERR_UNSUPPORTED, "predicate %d: PatternMatch over this column type is not supported", p);
-            if (t == DQ_TYPE_DECIMAL && (columns[c].decimal_scale < 0 || columns[c].decimal_scale > 18))
-                return fail(ctx, DQ_ERR_UNSUPPORTED, "predicate %d: PatternMatch over a DECIMAL of scale %d", p,
-                            columns[c].decimal_scale);
-            col_used[c] = 1;
-            continue;
-        }
-        int depth = 0, maxd = 0;
-        for (int k = 0; k < pr.code_len; k += 2) {
-            const int op = pr.code[k], arg = pr.code[k + 1];
-            if (op == DQ_P_COL) {
-                if (!col_ok(arg)) return fail(ctx, DQ_ERR_PREDICATE, "predicate %d: bad column %d", p, arg);
-                if (columns[arg].spark_type == DQ_TYPE_DECIMAL128)
-                    return fail(ctx, DQ_ERR_UNSUPPORTED, "predicate %d: a predicate cannot read DECIMAL128 column %d", p, arg);
-                col_used[arg] = 1;
-                ++depth;
-            } else if (op == DQ_P_CONST || op == DQ_P_NULL) {
-                if (op == DQ_P_CONST && (arg < 0 || arg >= pr.n_consts)) return fail(ctx, DQ_ERR_PREDICATE, "predicate %d: bad constant", p);
-                ++depth;
-            } else if (op == DQ_P_REGEX) {
-                return fail(ctx, DQ_ERR_PREDICATE, "predicate %d: REGEX is only supported as [COL, REGEX]", p);
-            } else if (op == DQ_P_IN) {
-                depth -= arg;
-            } else if (op == DQ_P_COALESCE) {
-                depth -= arg - 1;
-            } else if (op == DQ_P_CASE) {
-                if (arg < 2) return fail(ctx, DQ_ERR_PREDICATE, "predicate %d: CASE without WHEN", p);
-                depth -= arg - 1;  // 2 * #WHEN + has ELSE operands -> 1
-            } else if (op == DQ_P_SUBSTR) {
-                depth -= 2;
-            } else if (op == DQ_P_NOT || op == DQ_P_IS_NULL || op == DQ_P_IS_NOT_NULL || op == DQ_P_NEG ||
-                       op == DQ_P_LIKE || op == DQ_P_LENGTH || op == DQ_P_CAST_DOUBLE || op == DQ_P_CAST_LONG ||
-                       op == DQ_P_CAST_STRING_NUM || op == DQ_P_RLIKE || op == DQ_P_LOWER || op == DQ_P_UPPER ||
-                       op == DQ_P_TRIM || op == DQ_P_ISNAN || op == DQ_P_ABS || op == DQ_P_YEAR || op == DQ_P_MONTH ||
-                       op == DQ_P_DAY) {
-                if (op == DQ_P_LIKE && (arg < 0 || arg >= pr.n_consts)) return fail(ctx, DQ_ERR_PREDICATE, "predicate %d: bad LIKE pattern", p);
-                if (op == DQ_P_RLIKE &&
-                    (arg < 0 || arg >= pr.n_consts || pr.consts[arg].tag != DQ_V_STRING || pr.consts[arg].str_offset < 0 ||
-                     (pr.consts[arg].str_offset & 3) ||
-                     pr.consts[arg].str_offset + pr.consts[arg].str_len > pr.strings_len ||
-                     !dq::rx::rx_image_ok(pr.strings + pr.consts[arg].str_offset, pr.consts[arg].str_len)))
-                    return fail(ctx, DQ_ERR_PREDICATE, "predicate %d: malformed RLIKE program", p);
-            } else {
-                --depth;
-            }
-            if (depth < 1) return fail(ctx, DQ_ERR_PREDICATE, "predicate %d: stack underflow", p);
-            maxd = std::max(maxd, depth);
-        }
-        if (depth != 1 || maxd > kPredStack) return fail(ctx, DQ_ERR_PREDICATE, "predicate %d: malformed program", p);
-    }
+    // validate, plan, geometry, layout: pure host functions of the arguments (scan_plan.cpp)
+    ScanCall sc{ctx, columns, ncols, nrows, ops, nops, preds, npreds};
+    std::string msg;
+    int rc = validate_scan(columns, ncols, nrows, ops, nops, preds, npreds, &sc.use, &msg);
+    if (rc) return fail(ctx, rc, "%s", msg.c_str());
+    // DQ_WHERE_MASKS=0 / DQ_PRED_VM=1: the bitmap pass for every `where`; DQ_WHERE_FUSED=0: every masked filter from
+    // where_masks_kernel, the filter column a consumer (A/B runs; read per call)
+    const char* masks = getenv("DQ_WHERE_MASKS");
+    const char* fused = getenv("DQ_WHERE_FUSED");
+    sc.options.where_masks = !(masks && masks[0] == '0');
+    sc.options.fused_producer = !(fused && fused[0] == '0');
+    sc.options.pred_vm = pred_vm_forced();
+    rc = plan_scan(columns, ncols, nrows, ops, nops, preds, npreds, sc.use, sc.options, &sc.plan, &msg);
+    if (rc) return fail(ctx, rc, "%s", msg.c_str());
+    if ((rc = scan_geometry(sc))) return rc;
+    sc.L = layout_scan(sc.plan, sc.geo, sc.use, columns, ncols, nrows, nops, preds, npreds, flags & DQ_SCAN_OUT_DEVICE);
+    if ((rc = ensure_arena(ctx, sc.L.arena_bytes))) return rc;
+    if ((rc = ensure_pinned(ctx, sc.L.pinned_bytes))) return rc;
 
-    // ---- plan: column uses -> slots -----------------------------------------------------------
-    struct Use {
-        uint32_t flags = 0;
-        int slot = -1, pos = 0, hll = -1;
-        int pred_op = 0, pred_kind = FP_NONE, pred_src = -1;  // fused `col <op> const` Compliance predicate
-        int64_t pred_i = 0;
-        double pred_d = 0.0;
-    };
-    std::map<std::pair<int, int>, Use> uses;  // (column, where) -> use
-    std::vector<int> fused_col(nops, -1);     // Compliance ops answered inside a value slot
-    for (int i = 0; i < nops; ++i) {
-        const dq_op& op = ops[i];
-        if (wide_op[i]) continue;
-        const auto key = std::make_pair(op.column[0], op.where);
-        switch (op.kind) {
-            case DQ_OP_MEAN: case DQ_OP_SUM: case DQ_OP_MINIMUM: case DQ_OP_MAXIMUM: uses[key].flags |= CF_STATS; break;
-            case DQ_OP_STANDARD_DEVIATION: uses[key].flags |= CF_MOMENTS; break;
-            case DQ_OP_APPROX_COUNT_DISTINCT:
-                if (columns[op.column[0]].spark_type != DQ_TYPE_STRING) uses[key].flags |= CF_HLL;
-                break;
-            case DQ_OP_COMPLIANCE: {
-                // `col <op> const` on a non-decimal numeric column: evaluate inside that column's scan.
-                const dq_predicate& pr = preds[op.predicate];
-                if (pr.code_len != 6) break;
-                int a = pr.code[0], aa = pr.code[1], b = pr.code[2], ba = pr.code[3], cmp = pr.code[4];
-                if (cmp < DQ_P_EQ || cmp > DQ_P_GE) break;
-                if (a == DQ_P_CONST && b == DQ_P_COL) {  // const <op> col  ->  col <op'> const
-                    std::swap(a, b);
-                    std::swap(aa, ba);
-                    if (cmp == DQ_P_LT) cmp = DQ_P_GT;
-                    else if (cmp == DQ_P_GT) cmp = DQ_P_LT;
-                    else if (cmp == DQ_P_LE) cmp = DQ_P_GE;
-                    else if (cmp == DQ_P_GE) cmp = DQ_P_LE;
-                }
-                if (a != DQ_P_COL || b != DQ_P_CONST || ba < 0 || ba >= pr.n_consts) break;
-                const dq_const& k = pr.consts[ba];
-                const int t = columns[aa].spark_type;
-                if (!(t >= DQ_TYPE_BYTE && t <= DQ_TYPE_DOUBLE) || (k.tag != DQ_V_LONG && k.tag != DQ_V_DOUBLE)) break;
-                Use& u = uses[std::make_pair(aa, op.where)];
-                const int kind = k.tag == DQ_V_LONG ? FP_LONG : FP_DOUBLE;
-                if (u.pred_kind != FP_NONE &&
-                    !(u.pred_op == cmp && u.pred_kind == kind && u.pred_i == k.i64 &&
-                      (kind == FP_LONG || u.pred_d == k.f64)))
-                    break;  // one fused predicate per column scan; others use the predicate VM
-                u.pred_op = cmp;
-                u.pred_kind = kind;
-                u.pred_i = k.i64;
-                u.pred_d = k.f64;
-                fused_col[i] = aa;
-                break;
-            }
-            default: break;
-        }
-    }
-    std::vector<SlotDesc> slots;
-    auto new_slot = [&](int kind) {
-        SlotDesc sd;
-        memset(&sd, 0, sizeof(sd));
-        sd.kind = kind;
-        sd.col[0].hll_slot = sd.col[1].hll_slot = -1;
-        sd.col[0].elem = sd.col[1].elem = ET_NONE;
-        sd.rows_per_load = 8;
-        slots.push_back(sd);
-        return (int)slots.size() - 1;
-    };
-    struct PairKey { int x, y, w; bool operator<(const PairKey& o) const { return std::tie(x, y, w) < std::tie(o.x, o.y, o.w); } };
-    std::map<PairKey, int> pair_slots;  // (x, y, where) -> slot with corr
-    std::vector<std::pair<int, int>> op_slot(nops, {-1, 0});  // slot, colpos (corr: 1 = swapped)
-    // Correlation pairs first: fuse both columns' uses into one pair slot when element sizes match.
-    for (int i = 0; i < nops; ++i) {
-        const dq_op& op = ops[i];
-        if (op.kind != DQ_OP_CORRELATION) continue;
-        const int x = op.column[0], y = op.column[1], w = op.where;
-        auto it = pair_slots.find({x, y, w});
-        if (it != pair_slots.end()) { op_slot[i] = {it->second, 0}; continue; }
-        it = pair_slots.find({y, x, w});
-        if (it != pair_slots.end()) { op_slot[i] = {it->second, 1}; continue; }
-        const int ex = elem_of(columns[x].spark_type), ey = elem_of(columns[y].spark_type);
-        const int s = new_slot(SK_VALUES);
-        slots[s].ncols = 2;
-        slots[s].corr = 1;
-        slots[s].rows_per_load = elem_size(ex) == elem_size(ey) ? rows_per_load_of(ex) : 8;
-        slots[s].col[0].elem = ex;
-        slots[s].col[1].elem = ey;
-        if (x != y) {
-            auto ux = uses.find({x, w}), uy = uses.find({y, w});
-            if (ux != uses.end() && ux->second.slot < 0) { ux->second.slot = s; ux->second.pos = 0; }
-            if (uy != uses.end() && uy->second.slot < 0) { uy->second.slot = s; uy->second.pos = 1; }
-        }
-        slots[s].col[0].values = (const void*)(intptr_t)x;  // column index until pointers are known
-        slots[s].col[1].values = (const void*)(intptr_t)y;
-        slots[s].where_t = (const uint64_t*)(intptr_t)(w + 1);
-        pair_slots[{x, y, w}] = s;
-        op_slot[i] = {s, 0};
-    }
-    for (auto& kv : uses) {
-        if (kv.second.slot >= 0) continue;
-        const int c = kv.first.first, w = kv.first.second;
-        const int s = new_slot(SK_VALUES);
-        slots[s].ncols = 1;
-        slots[s].rows_per_load = rows_per_load_of(elem_of(columns[c].spark_type));
-        slots[s].col[0].elem = elem_of(columns[c].spark_type);
-        slots[s].col[0].values = (const void*)(intptr_t)c;
-        slots[s].where_t = (const uint64_t*)(intptr_t)(w + 1);
-        kv.second.slot = s;
-        kv.second.pos = 0;
-    }
-    int nhll = 0;
-    for (auto& kv : uses) {
-        SlotDesc& sd = slots[kv.second.slot];
-        sd.col[kv.second.pos].flags |= kv.second.flags;
-        sd.col[kv.second.pos].pred_op = kv.second.pred_op;
-        sd.col[kv.second.pos].pred_kind = kv.second.pred_kind;
-        sd.col[kv.second.pos].pred_i = kv.second.pred_i;
-        sd.col[kv.second.pos].pred_d = kv.second.pred_d;
-        if (kv.second.flags & CF_HLL) {
-            kv.second.hll = nhll++;
-            sd.col[kv.second.pos].hll_slot = kv.second.hll;
-        }
-    }
-    // String-shaped ops -> string slots (column, where): MinLength/MaxLength, DataType, string HLL.
-    std::vector<StrSlot> sslots;
-    std::map<std::pair<int, int>, int> sslot_of;
-    std::vector<int> op_sslot(nops, -1);
-    for (int i = 0; i < nops; ++i) {
-        const dq_op& op = ops[i];
-        if (wide_op[i]) continue;
-        const bool str_hll = op.kind == DQ_OP_APPROX_COUNT_DISTINCT && columns[op.column[0]].spark_type == DQ_TYPE_STRING;
-        if (!(op.kind == DQ_OP_MIN_LENGTH || op.kind == DQ_OP_MAX_LENGTH || op.kind == DQ_OP_DATATYPE || str_hll)) continue;
-        const auto key = std::make_pair(op.column[0], op.where);
-        auto it = sslot_of.find(key);
-        if (it == sslot_of.end()) {
-            StrSlot ss;
-            memset(&ss, 0, sizeof(ss));
-            ss.spark_type = columns[op.column[0]].spark_type;
-            ss.decimal_scale = columns[op.column[0]].decimal_scale;
-            ss.hll_slot = -1;
-            ss.values = (const void*)(intptr_t)op.column[0];  // column index until pointers are known
-            ss.where_t = (const uint64_t*)(intptr_t)(op.where + 1);
-            sslots.push_back(ss);
-            it = sslot_of.emplace(key, (int)sslots.size() - 1).first;
-        }
-        StrSlot& ss = sslots[it->second];
-        if (op.kind == DQ_OP_DATATYPE) ss.flags |= SF_DTYPE;
-        else if (str_hll) {
-            ss.flags |= SF_HLL;
-            if (ss.hll_slot < 0) ss.hll_slot = nhll++;
-        } else ss.flags |= SF_LEN;
-        op_sslot[i] = it->second;
-    }
-    const int nsslots = (int)sslots.size();
-    std::vector<StrOpMap> sopmap;
-    for (int i = 0; i < nops; ++i) {
-        if (op_sslot[i] < 0 || ops[i].kind == DQ_OP_APPROX_COUNT_DISTINCT) continue;
-        StrOpMap m;
-        m.op = i;
-        m.kind = ops[i].kind;
-        m.slot = op_sslot[i];
-        m.pad = 0;
-        sopmap.push_back(m);
-    }
-
-    // DECIMAL128 ops -> decimal128 slots (column, where), one launch for all of them (decimal128.hip).
-    std::vector<D128Slot> dslots128;
-    std::map<std::pair<int, int>, int> dslot_of;
-    std::vector<D128OpMap> dopmap;
-    std::vector<int> op_dslot(nops, -1);
-    for (int i = 0; i < nops; ++i) {
-        if (!wide_op[i]) continue;
-        const dq_op& op = ops[i];
-        const auto key = std::make_pair(op.column[0], op.where);
-        auto it = dslot_of.find(key);
-        if (it == dslot_of.end()) {
-            D128Slot ds;
-            memset(&ds, 0, sizeof(ds));
-            ds.hll_slot = -1;
-            ds.scale = columns[op.column[0]].decimal_scale;
-            ds.values = (const void*)(intptr_t)op.column[0];  // column index until pointers are known
-            ds.where_t = (const uint64_t*)(intptr_t)(op.where + 1);
-            dslots128.push_back(ds);
-            it = dslot_of.emplace(key, (int)dslots128.size() - 1).first;
-        }
-        D128Slot& ds = dslots128[it->second];
-        op_dslot[i] = it->second;
-        switch (op.kind) {
-            case DQ_OP_MEAN: case DQ_OP_SUM: ds.flags |= DF_SUM; break;
-            case DQ_OP_MINIMUM: case DQ_OP_MAXIMUM: ds.flags |= DF_MINMAX; break;
-            case DQ_OP_STANDARD_DEVIATION: ds.flags |= DF_MOMENTS; break;
-            case DQ_OP_APPROX_COUNT_DISTINCT:
-                ds.flags |= DF_HLL;
-                if (ds.hll_slot < 0) ds.hll_slot = nhll++;
-                break;
-            default: break;
-        }
-        if (op.kind != DQ_OP_APPROX_COUNT_DISTINCT) {  // the HLL state is packed by finalize_kernel
-            D128OpMap m;
-            m.op = i;
-            m.kind = op.kind;
-            m.slot = it->second;
-            m.has_where = op.where >= 0;
-            dopmap.push_back(m);
-        }
-    }
-    const int ndslots = (int)dslots128.size();
-
-    // `where` filters evaluated inside the scan (WhereOut, dq_internal.h): every simple predicate used as a `where`
-    // (DQ_WHERE_MASKS=0 or DQ_PRED_VM=1: the bitmap pass for all of them, for A/B runs).
-    std::vector<char> wmasked(npreds, 0);
-    std::vector<PredSimple> wprog(npreds);
-    {
-        const char* e = getenv("DQ_WHERE_MASKS");
-        const bool masks_on = !pred_vm_forced() && !(e && e[0] == '0');
-        for (int i = 0; i < nops && masks_on; ++i) {
-            const int p = ops[i].where;
-            if (p < 0 || wmasked[p]) continue;
-            const dq_predicate& pr = preds[p];
-            if (pr.code_len == 4 && pr.code[2] == DQ_P_REGEX) continue;
-            if (compile_simple_predicate(pr, columns, ncols, wprog[p])) wmasked[p] = 1;
-        }
-    }
-
-    // Ops -> OpMap; bits-only slots for Size(where), Completeness of unread columns, Compliance.
-    std::vector<OpMap> opmap(nops);
-    std::map<std::tuple<int, int, int>, int> bits_slots;  // (kind, col/pred, where) -> slot
-    auto bits_slot = [&](int tag, int ref, int w) {
-        auto key = std::make_tuple(tag, ref, w);
-        auto it = bits_slots.find(key);
-        if (it != bits_slots.end()) return it->second;
-        const int s = new_slot(SK_BITS);
-        slots[s].where_t = (const uint64_t*)(intptr_t)(w + 1);
-        slots[s].col[0].values = (const void*)(intptr_t)ref;
-        slots[s].col[0].flags = (uint32_t)tag;  // 1 = completeness column, 2 = compliance predicate, 0 = size
-        bits_slots[key] = s;
-        return s;
-    };
-    for (int i = 0; i < nops; ++i) {
-        const dq_op& op = ops[i];
-        OpMap& m = opmap[i];
-        memset(&m, 0, sizeof(m));
-        m.kind = op.kind;
-        m.slot = -1;
-        m.hll_slot = -1;
-        m.has_where = op.where >= 0;
-        m.nrows = nrows;
-        const int c = op.column[0];
-        if (op.kind != DQ_OP_SIZE && op.kind != DQ_OP_COMPLIANCE && col_ok(c)) {
-            const int t = columns[c].spark_type;
-            m.is_float = (t == DQ_TYPE_FLOAT || t == DQ_TYPE_DOUBLE);
-            m.decimal_scale = t == DQ_TYPE_DECIMAL ? columns[c].decimal_scale : 0;
-        }
-        m.wslot = -1;
-        if (wide_op[i]) {  // written by finalize_decimal128_kernel; the HLL words by finalize_kernel
-            if (op.kind == DQ_OP_APPROX_COUNT_DISTINCT) m.hll_slot = dslots128[op_dslot[i]].hll_slot;
-            continue;
-        }
-        const bool masked_where = op.where >= 0 && wmasked[op.where];
-        switch (op.kind) {
-            case DQ_OP_SIZE:
-                if (op.where >= 0 && !masked_where) m.slot = bits_slot(0, -1, op.where);
-                break;
-            case DQ_OP_COMPLIANCE:
-                if (fused_col[i] >= 0) {
-                    const Use& u = uses.at({fused_col[i], op.where});
-                    m.slot = u.slot;
-                    m.colpos = u.pos;
-                    m.from_bits = 3;  // fused predicate: matches = c.pt, non-null rows = c.n
-                } else {
-                    m.slot = bits_slot(2, op.predicate, op.where);
-                }
-                break;
-            case DQ_OP_COMPLETENESS: {
-                auto it = uses.find({c, op.where});
-                if (it != uses.end()) {
-                    m.slot = it->second.slot;
-                    m.colpos = it->second.pos;
-                } else if (columns[c].validity == nullptr) {
-                    m.from_bits = 2;  // all rows valid: matches = conditionalCount
-                    if (op.where >= 0 && !masked_where) m.slot = bits_slot(0, -1, op.where);
-                } else {
-                    m.slot = bits_slot(1, c, op.where);
-                    m.from_bits = 1;
-                }
-                break;
-            }
-            case DQ_OP_CORRELATION:
-                m.slot = op_slot[i].first;
-                m.colpos = op_slot[i].second;
-                break;
-            case DQ_OP_MIN_LENGTH: case DQ_OP_MAX_LENGTH: case DQ_OP_DATATYPE:
-                break;  // written by finalize_strings_kernel
-            default: {
-                if (op_sslot[i] >= 0) {  // ApproxCountDistinct of a string column
-                    m.hll_slot = sslots[op_sslot[i]].hll_slot;
-                    break;
-                }
-                const Use& u = uses.at({c, op.where});
-                m.slot = u.slot;
-                m.colpos = u.pos;
-                m.hll_slot = u.hll;
-                break;
-            }
-        }
-    }
-    // Masked `where` plan: the producer (a one-column 8-byte value slot under the filter whose terms read only that
-    // column, else an SK_WHERE slot filled by where_masks_kernel), the consumer masks, and whether bits / string
-    // slots still read the filter's bitmaps.
-    struct WherePlan {
-        int producer = -1;           // value slot evaluating the filter inside its scan
-        int wslot = -1;              // slot holding the TRUE / NOT-NULL counts
-        bool bitmaps = false;
-        std::vector<int> mask_col;   // consumer columns, one mask each
-    };
-    std::vector<WherePlan> wplan(npreds);
-    std::vector<std::pair<int, int>> slot_masks(slots.size() * 2, {-1, -1});  // (slot, k) -> (pred, mask index)
-    std::vector<int> slot_producer_of(slots.size(), -1);
-    auto slot_where = [&](const SlotDesc& sd) { return (int)(intptr_t)sd.where_t - 1; };
-    for (int p = 0; p < npreds; ++p) {
-        if (!wmasked[p]) continue;
-        WherePlan& wp = wplan[p];
-        int depth = 0, maxd = 0;
-        for (int i = 0; i < wprog[p].nb; ++i) {
-            depth += wprog[p].b[i] >= 0 ? 1 : (wprog[p].b[i] == kPB_NOT ? 0 : -1);
-            maxd = std::max(maxd, depth);
-        }
-        // (DQ_WHERE_FUSED=0: every masked filter from where_masks_kernel, the filter column a consumer -- A/B runs)
-        const bool fuse_producer = !(getenv("DQ_WHERE_FUSED") && getenv("DQ_WHERE_FUSED")[0] == '0');
-        for (int s = 0; s < (int)slots.size() && wp.producer < 0 && maxd <= kWhereStack && fuse_producer; ++s) {
-            const SlotDesc& sd = slots[s];
-            if (sd.kind != SK_VALUES || sd.ncols != 1 || slot_where(sd) != p) continue;
-            const int x = (int)(intptr_t)sd.col[0].values;
-            const int t = columns[x].spark_type;
-            if (!(t == DQ_TYPE_LONG || t == DQ_TYPE_TIMESTAMP || t == DQ_TYPE_DOUBLE)) continue;
-            bool own = true;
-            for (int k = 0; k < wprog[p].nterms; ++k) own &= wprog[p].t[k].col == x;
-            if (own) wp.producer = s;
-        }
-        for (int s = 0; s < (int)slots.size(); ++s) {
-            SlotDesc& sd = slots[s];
-            if (sd.kind == SK_BITS && (slot_where(sd) == p || ((int)sd.col[0].flags == 2 && (int)(intptr_t)sd.col[0].values == p)))
-                wp.bitmaps = true;
-            if (sd.kind != SK_VALUES || slot_where(sd) != p) continue;
-            if (s == wp.producer) continue;
-            for (int k = 0; k < sd.ncols; ++k) {
-                const int c = (int)(intptr_t)sd.col[k].values;
-                auto it = std::find(wp.mask_col.begin(), wp.mask_col.end(), c);
-                int mi = (int)(it - wp.mask_col.begin());
-                if (it == wp.mask_col.end()) wp.mask_col.push_back(c);
-                slot_masks[2 * s + k] = {p, mi};
-            }
-        }
-        for (const StrSlot& ss : sslots)
-            if ((int)(intptr_t)ss.where_t - 1 == p) wp.bitmaps = true;
-        for (const D128Slot& ds : dslots128)
-            if ((int)(intptr_t)ds.where_t - 1 == p) wp.bitmaps = true;
-        if ((int)wp.mask_col.size() > kWhereMasks) {  // too many consumers for one producer: the bitmap pass
-            wmasked[p] = 0;
-            wp = WherePlan();
-            for (auto& sm : slot_masks)
-                if (sm.first == p) sm = {-1, -1};
-            continue;
-        }
-    }
-    // Size(where) / from_bits == 2 Completeness were planned without a bits slot for masked filters: give back the
-    // bits slots to filters that fell back above.
-    for (int i = 0; i < nops; ++i) {
-        const dq_op& op = ops[i];
-        if (op.where < 0 || wmasked[op.where] || opmap[i].slot >= 0) continue;
-        if (op.kind == DQ_OP_SIZE || (op.kind == DQ_OP_COMPLETENESS && opmap[i].from_bits == 2))
-            opmap[i].slot = bits_slot(0, -1, op.where);
-    }
-    slot_masks.resize(slots.size() * 2, {-1, -1});
-    slot_producer_of.resize(slots.size(), -1);
-    for (int p = 0; p < npreds; ++p) {
-        if (!wmasked[p]) continue;
-        WherePlan& wp = wplan[p];
-        if (wp.producer >= 0) {
-            wp.wslot = wp.producer;
-            slot_producer_of[wp.producer] = p;
-            slots[wp.producer].where_t = nullptr;
-        } else {
-            wp.wslot = new_slot(SK_WHERE);
-            slot_masks.resize(slots.size() * 2, {-1, -1});
-            slot_producer_of.resize(slots.size(), -1);
-        }
-        for (int s = 0; s < (int)slots.size(); ++s)
-            if (slots[s].kind == SK_VALUES && slot_where(slots[s]) == p) slots[s].where_t = nullptr;
-    }
-    for (int i = 0; i < nops; ++i) {
-        const int p = ops[i].where;
-        if (p >= 0) opmap[i].wslot = wmasked[p] ? wplan[p].wslot : opmap[i].slot;
-    }
-    const int nslots = (int)slots.size();
-    if (nslots > kMaxSlots) return fail(ctx, DQ_ERR_UNSUPPORTED, "too many slots (%d)", nslots);
-    // Predicates evaluated by the VM pass: `where` filters and Compliance predicates not fused into
-    // a value scan.
-    std::fill(pred_used.begin(), pred_used.end(), 0);
-    for (int i = 0; i < nops; ++i) {
-        if (ops[i].where >= 0) pred_used[ops[i].where] = 1;
-        if (ops[i].kind == DQ_OP_COMPLIANCE && fused_col[i] < 0) pred_used[ops[i].predicate] = 1;
-    }
-    // pred_used: the predicate gets TRUE / NOT-NULL bitmaps (allocated); pred_pass: a predicate pass writes them (a
-    // masked `where` writes them from its producer, only when something reads them)
-    std::vector<char> pred_pass(pred_used);
-    int nstandalone = 0;
-    for (int p = 0; p < npreds; ++p) {
-        if (!wmasked[p]) continue;
-        pred_pass[p] = 0;
-        if (!wplan[p].bitmaps) pred_used[p] = 0;
-        if (wplan[p].producer < 0) ++nstandalone;
-    }
-
-    // ---- device memory layout -----------------------------------------------------------------
-    // Launch groups: one kernel launch per slot shape; each gets a grid sized to fill the chip once.
-    const int64_t ntiles = (nrows + kTileRows - 1) / kTileRows;
-    struct Group { int kind, P, nc; bool f0, f1; int heavy; int grid; std::vector<int32_t> slots; };
-    std::vector<Group> groups;
-    auto shape_key = [](int kind, int P, int nc, bool f0, bool f1, int heavy) {
-        return (((((kind * 16 + P) * 4 + nc) * 2 + f0) * 2 + f1) * 4 + heavy);
-    };
-    // heavy 2 (8-byte columns only): every column carries stats, moments, HLL and a fused compare the heavy kernel
-    // evaluates on its fast path, pairs carry the correlation, and there is no `where` -> the branch-free variant
-    auto full_col = [](const ColDesc& c) {
-        const bool fl = c.elem == ET_F64;
-        const uint32_t all = CF_STATS | CF_MOMENTS | CF_HLL;
-        const bool fast_pred = fl ? (c.pred_kind != FP_NONE && (c.pred_kind == FP_LONG || c.pred_d == c.pred_d))
-                                  : c.pred_kind == FP_LONG;
-        return (c.flags & all) == all && fast_pred;
-    };
-    std::map<int, int> group_of;
-    const int64_t grid_cap = scan_grid_cap();
-    for (int s = 0; s < (int)slots.size(); ++s) {
-        const SlotDesc& sd = slots[s];
-        if (sd.kind == SK_WHERE) continue;
-        const bool f0 = sd.kind == SK_VALUES && (sd.col[0].elem == ET_F32 || sd.col[0].elem == ET_F64);
-        const bool f1 = sd.kind == SK_VALUES && sd.ncols > 1 && (sd.col[1].elem == ET_F32 || sd.col[1].elem == ET_F64);
-        const int P = sd.kind == SK_VALUES ? sd.rows_per_load : 8;
-        const int nc = sd.kind == SK_VALUES ? sd.ncols : 1;
-        // HLL registers or a fused predicate need the larger (HEAVY) kernel instantiation.
-        int heavy = 0;
-        for (int k = 0; sd.kind == SK_VALUES && k < sd.ncols; ++k)
-            if ((sd.col[k].flags & CF_HLL) || sd.col[k].pred_kind != FP_NONE) heavy = 1;
-        if (heavy && P == 2 && sd.where_t == nullptr && (sd.ncols == 1 || sd.corr)) {
-            bool full = true;
-            for (int k = 0; k < sd.ncols; ++k) full &= full_col(sd.col[k]);
-            if (full) heavy = 2;
-        }
-        if (slot_producer_of[s] >= 0) heavy = 3;
-        const int kind = sd.kind;
-        const int key = shape_key(kind, P, nc, f0, f1, heavy);
-        auto it = group_of.find(key);
-        if (it == group_of.end()) {
-            int occ;
-            auto oc = ctx->occupancy.find(key);
-            if (oc != ctx->occupancy.end()) occ = oc->second;
-            else occ = ctx->occupancy[key] = std::max(1, scan_group_blocks_per_cu(kind, P, nc, f0, f1, heavy));
-            const int64_t planned = std::max<int64_t>(1, std::min<int64_t>(std::max<int64_t>(ntiles, 1), (int64_t)ctx->cus * occ));
-            const int64_t grid = std::min(planned, grid_cap);
-            groups.push_back(Group{kind, P, nc, f0, f1, heavy, (int)grid, {}});
-            it = group_of.emplace(key, (int)groups.size() - 1).first;
-        }
-        groups[it->second].slots.push_back(s);
-    }
-    // concurrent launches: each shape gets its share of the chip so the launches are co-resident
-    const int nlaunch = (int)groups.size() + (nsslots ? 1 : 0);
-    const bool concurrent = scan_concurrency() && nlaunch > 1 && ensure_side_streams(ctx) == DQ_OK;
-    if (concurrent)
-        for (Group& g : groups) g.grid = std::max(1, (g.grid + nlaunch - 1) / nlaunch);
-    int gstride = 1;
-    for (const Group& g : groups) gstride = std::max(gstride, g.grid);
-    int sgrid = nsslots ? string_scan_grid(ctx->cus, nrows) : 0;
-    if (concurrent && sgrid) sgrid = std::max(1, (sgrid + nlaunch - 1) / nlaunch);
-    gstride = std::max(gstride, sgrid);
-    // the decimal128 launch runs on the ctx stream after the other launches joined: the whole chip
-    const int dgrid = ndslots ? decimal128_scan_grid(ctx->cus, nrows) : 0;
-    gstride = std::max(gstride, dgrid);
-    // producers first: their masks are read by the other launches
-    std::stable_sort(groups.begin(), groups.end(), [](const Group& a, const Group& b) { return (a.heavy == 3) > (b.heavy == 3); });
-    std::vector<int32_t> slot_nblocks(std::max<size_t>(slots.size(), 1), 1);
-    for (const Group& g : groups)
-        for (int32_t s : g.slots) slot_nblocks[s] = g.grid;
-    const int64_t wchunks = (padded_words_for(nrows) + 7) / 8;  // where_masks_kernel: 8 words per wave, 4 waves
-    const int wgrid = (int)std::max<int64_t>(1, std::min<int64_t>((wchunks + 3) / 4, gstride));
-    for (int p = 0; p < npreds; ++p)
-        if (wmasked[p] && wplan[p].producer < 0) slot_nblocks[wplan[p].wslot] = wgrid;
-    std::vector<int32_t> hll_nblocks(std::max(nhll, 1), 1);
-    for (const auto& kv : uses)
-        if (kv.second.hll >= 0) hll_nblocks[kv.second.hll] = slot_nblocks[kv.second.slot];
-    for (const StrSlot& ss : sslots)
-        if (ss.hll_slot >= 0) hll_nblocks[ss.hll_slot] = sgrid;
-    for (const D128Slot& ds : dslots128)
-        if (ds.hll_slot >= 0) hll_nblocks[ds.hll_slot] = dgrid;
-    const int64_t pwords = padded_words_for(nrows);
-    const size_t bitmap_bytes = (size_t)(nrows + 7) / 8;
-
-    std::vector<const void*> dval(ncols, nullptr), dvalid(ncols, nullptr), doffs(ncols, nullptr);
-    size_t arena_need = 0;
-    std::vector<size_t> stage_off(ncols, 0);
-    int npred_pass = 0;
-    for (int p = 0; p < npreds; ++p) npred_pass += pred_pass[p];
-    for (int pass = 0; pass < 2; ++pass) {
-        Bump b;
-        b.base = pass ? ctx->arena : nullptr;
-        for (int c = 0; c < ncols; ++c) {
-            const dq_column& col = columns[c];
-            if (!col_used[c]) continue;
-            if (col.flags & DQ_COL_DEVICE) {
-                dval[c] = col.values;
-                dvalid[c] = col.validity;
-                doffs[c] = col.offsets;
-                continue;
-            }
-            size_t vbytes;
-            if (col.spark_type == DQ_TYPE_STRING) vbytes = nrows > 0 ? (size_t)col.offsets[nrows] : 0;
-            else if (col.spark_type == DQ_TYPE_DECIMAL128) vbytes = (size_t)nrows * 16;
-            else vbytes = (size_t)nrows * elem_size(elem_of(col.spark_type));
-            void* v = b.take(vbytes + 16);
-            void* vd = col.validity ? b.take(align_up(bitmap_bytes, 8) + 8) : nullptr;
-            void* od = col.spark_type == DQ_TYPE_STRING ? b.take(((size_t)nrows + 1) * 4) : nullptr;
-            if (pass) {
-                if (vbytes) DQ_HIP(ctx, hipMemcpyAsync(v, col.values, vbytes, hipMemcpyHostToDevice, ctx->stream));
-                if (vd && bitmap_bytes) DQ_HIP(ctx, hipMemcpyAsync(vd, col.validity, bitmap_bytes, hipMemcpyHostToDevice, ctx->stream));
-                if (od) DQ_HIP(ctx, hipMemcpyAsync(od, col.offsets, ((size_t)nrows + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-                dval[c] = v;
-                dvalid[c] = col.validity ? vd : nullptr;
-                doffs[c] = od;
-            }
-        }
-        // predicate outputs + programs
-        std::vector<uint64_t*> pt(npreds, nullptr), pn(npreds, nullptr);
-        for (int p = 0; p < npreds; ++p) {
-            if (!pred_used[p]) continue;
-            pt[p] = (uint64_t*)b.take((size_t)pwords * 8);
-            pn[p] = (uint64_t*)b.take((size_t)pwords * 8);
-        }
-        // masked `where`: the producer's descriptor and one mask per consumer column
-        std::vector<WhereOut*> wodev(npreds, nullptr);
-        std::vector<std::vector<uint64_t*>> wmask(npreds);
-        for (int p = 0; p < npreds; ++p) {
-            if (!wmasked[p]) continue;
-            wodev[p] = (WhereOut*)b.take(sizeof(WhereOut));
-            for (size_t m = 0; m < wplan[p].mask_col.size(); ++m) wmask[p].push_back((uint64_t*)b.take((size_t)pwords * 8));
-        }
-        void* pcols = b.take(sizeof(PredColumn) * std::max(ncols, 1));
-        int32_t* rx_status = (int32_t*)b.take(sizeof(int32_t) * std::max(npreds, 1));
-        std::vector<void*> pprog(npreds, nullptr), pcode(npreds, nullptr), pconst(npreds, nullptr), pstr(npreds, nullptr);
-        for (int p = 0; p < npreds; ++p) {
-            if (!pred_pass[p]) continue;
-            pprog[p] = b.take(sizeof(PredProgram));
-            pcode[p] = b.take(sizeof(int32_t) * preds[p].code_len);
-            pconst[p] = b.take(sizeof(dq_const) * std::max(preds[p].n_consts, 1));
-            pstr[p] = b.take(std::max<int64_t>(preds[p].strings_len, 1));
-        }
-        SlotDesc* dslots = (SlotDesc*)b.take(sizeof(SlotDesc) * std::max(nslots, 1));
-        OpMap* dops = (OpMap*)b.take(sizeof(OpMap) * nops);
-        SlotPartial* partials = (SlotPartial*)b.take(sizeof(SlotPartial) * (size_t)std::max(nslots, 1) * gstride);
-        int32_t* dgroups = (int32_t*)b.take(sizeof(int32_t) * std::max(nslots, 1));
-        int32_t* dslot_nb = (int32_t*)b.take(sizeof(int32_t) * slot_nblocks.size());
-        int32_t* dhll_nb = (int32_t*)b.take(sizeof(int32_t) * hll_nblocks.size());
-        SlotPartial* finals = (SlotPartial*)b.take(sizeof(SlotPartial) * std::max(nslots, 1));
-        uint8_t* hllp = (uint8_t*)b.take((size_t)std::max(nhll, 1) * gstride * kHllRegs);
-        uint8_t* hllf = (uint8_t*)b.take((size_t)std::max(nhll, 1) * kHllRegs);
-        dq_state* dout = (flags & DQ_SCAN_OUT_DEVICE) ? out : (dq_state*)b.take(sizeof(dq_state) * nops);
-        StrSlot* dsslots = (StrSlot*)b.take(sizeof(StrSlot) * std::max(nsslots, 1));
-        StrPartial* spartials = (StrPartial*)b.take(sizeof(StrPartial) * (size_t)std::max(nsslots, 1) * gstride);
-        StrOpMap* dsops = (StrOpMap*)b.take(sizeof(StrOpMap) * std::max<size_t>(sopmap.size(), 1));
-        D128Slot* ddslots = (D128Slot*)b.take(sizeof(D128Slot) * std::max(ndslots, 1));
-        D128Partial* dpartials = (D128Partial*)b.take(sizeof(D128Partial) * (size_t)std::max(ndslots, 1) * gstride);
-        D128OpMap* ddops = (D128OpMap*)b.take(sizeof(D128OpMap) * std::max<size_t>(dopmap.size(), 1));
-        if (!pass) {
-            arena_need = b.off;
-            int rc = ensure_arena(ctx, arena_need);
-            if (rc) return rc;
-            // plan bytes uploaded through pinned staging
-            size_t pin = sizeof(D128Slot) * std::max(ndslots, 1) + sizeof(D128OpMap) * std::max<size_t>(dopmap.size(), 1) + 64 +
-                         sizeof(int32_t) * std::max(npreds, 1) + 32 + sizeof(StrSlot) * std::max(nsslots, 1) + sizeof(StrOpMap) * std::max<size_t>(sopmap.size(), 1) +
-                         sizeof(PredColumn) * std::max(ncols, 1) + sizeof(SlotDesc) * std::max(nslots, 1) +
-                         sizeof(OpMap) * nops + sizeof(dq_state) * nops + 4 * (slot_nblocks.size() + hll_nblocks.size() + nslots) + 8192;
-            for (int p = 0; p < npreds; ++p)
-                if (wmasked[p]) pin += sizeof(WhereOut) + 256;
-            for (int p = 0; p < npreds; ++p)
-                if (pred_pass[p])
-                    pin += sizeof(PredProgram) + sizeof(int32_t) * preds[p].code_len +
-                           sizeof(dq_const) * std::max(preds[p].n_consts, 1) + std::max<int64_t>(preds[p].strings_len, 1) + 256;
-            rc = ensure_pinned(ctx, pin);
-            if (rc) return rc;
-            continue;
-        }
-        // ---- pass 1: fill descriptors, upload, launch ------------------------------------------
-        // The pinned buffer may still be read by a previous call's async copies: wait for them.
-        DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        Bump hb;
-        hb.base = ctx->pinned;
-        auto upload = [&](void* dst, const void* src, size_t n) -> int {
-            void* h = hb.take(n, 16);
-            memcpy(h, src, n);
-            DQ_HIP(ctx, hipMemcpyAsync(dst, h, n, hipMemcpyHostToDevice, ctx->stream));
-            return DQ_OK;
-        };
-        bool any_status = false;  // some predicate may set its status word: read the words back after the scan
-        if (npred_pass || nstandalone) {
-            DQ_HIP(ctx, hipMemsetAsync(rx_status, 0, sizeof(int32_t) * std::max(npreds, 1), ctx->stream));
-            std::vector<PredColumn> pc(std::max(ncols, 1));
-            for (int c = 0; c < ncols; ++c) {
-                memset(&pc[c], 0, sizeof(PredColumn));
-                pc[c].values = dval[c];
-                pc[c].validity = (const uint64_t*)dvalid[c];
-                pc[c].offsets = (const int32_t*)doffs[c];
-                pc[c].spark_type = columns[c].spark_type;
-                pc[c].elem = elem_of(columns[c].spark_type);
-                pc[c].decimal_scale = columns[c].decimal_scale;
-            }
-            int rc = upload(pcols, pc.data(), sizeof(PredColumn) * pc.size());
-            if (rc) return rc;
-            for (int p = 0; p < npreds; ++p) {
-                if (!pred_pass[p]) continue;
-                const dq_predicate& pr = preds[p];
-                rc = upload(pcode[p], pr.code, sizeof(int32_t) * pr.code_len);
-                if (rc) return rc;
-                if (pr.n_consts > 0) {
-                    rc = upload(pconst[p], pr.consts, sizeof(dq_const) * pr.n_consts);
-                    if (rc) return rc;
-                }
-                if (pr.strings_len > 0) {
-                    rc = upload(pstr[p], pr.strings, (size_t)pr.strings_len);
-                    if (rc) return rc;
-                }
-                PredProgram pg;
-                pg.code = (const int32_t*)pcode[p];
-                pg.consts = (const dq_const*)pconst[p];
-                pg.strings = (const uint8_t*)pstr[p];
-                pg.code_len = pr.code_len;
-                pg.n_consts = pr.n_consts;
-                rc = upload(pprog[p], &pg, sizeof(pg));
-                if (rc) return rc;
-                if (pr.code_len == 4 && pr.code[2] == DQ_P_REGEX) {
-                    const dq_const& k = pr.consts[pr.code[3]];
-                    launch_regex(pc[pr.code[1]], (const int32_t*)((const uint8_t*)pstr[p] + k.str_offset), nrows, pwords,
-                                 pt[p], pn[p], rx_status + p, ctx->stream);
-                    ctx->kernel_launches[DQ_KERNEL_REGEX]++;
-                    any_status = true;
-                } else if (PredSimple ps; !pred_vm_forced() && compile_simple_predicate(pr, columns, ncols, ps)) {
-                    launch_pred_simple(ps, (const PredColumn*)pcols, nrows, pwords, pt[p], pn[p], ctx->stream);
-                    ctx->kernel_launches[DQ_KERNEL_PRED_SIMPLE]++;
-                } else {
-                    // rx: the program holds RLIKE; str: it has a string operand, which a comparison, arithmetic or
-                    // CAST may have to convert to DOUBLE (a conversion the device cannot round exactly sets status)
-                    bool rx = false, str = false;
-                    for (int k = 0; k + 1 < pr.code_len; k += 2) {
-                        const int a = pr.code[k + 1];
-                        rx |= pr.code[k] == DQ_P_RLIKE;
-                        str |= pr.code[k] == DQ_P_COL && a >= 0 && a < ncols && columns[a].spark_type == DQ_TYPE_STRING;
-                        str |= pr.code[k] == DQ_P_CONST && a >= 0 && a < pr.n_consts && pr.consts[a].tag == DQ_V_STRING;
-                    }
-                    launch_predicate((const PredProgram*)pprog[p], rx, rx_status + p, (const PredColumn*)pcols, nrows,
-                                     pwords, pt[p], pn[p], ctx->stream);
-                    ctx->kernel_launches[DQ_KERNEL_PRED_VM]++;
-                    any_status |= rx || str;
-                }
-                DQ_HIP(ctx, hipGetLastError());
-            }
-        }
-        // masked `where` descriptors; the standalone producers run here, before every scan launch
-        for (int p = 0; p < npreds; ++p) {
-            if (!wmasked[p]) continue;
-            const WherePlan& wp = wplan[p];
-            WhereOut wo;
-            memset(&wo, 0, sizeof(wo));
-            wo.prog = wprog[p];
-            wo.nmasks = (int)wp.mask_col.size();
-            wo.bitmaps = wp.bitmaps ? 1 : 0;
-            wo.where_t = pt[p];
-            wo.where_nn = pn[p];
-            for (int m = 0; m < wo.nmasks; ++m) {
-                wo.valid[m] = (const uint64_t*)dvalid[wp.mask_col[m]];
-                wo.mask[m] = wmask[p][m];
-            }
-            int rc = upload(wodev[p], &wo, sizeof(wo));
-            if (rc) return rc;
-            if (wp.producer < 0) {
-                launch_where_masks(wodev[p], wprog[p], (const PredColumn*)pcols, nrows, pwords, partials, wp.wslot, gstride,
-                                   slot_nblocks[wp.wslot], ctx->stream);
-                DQ_HIP(ctx, hipGetLastError());
-                ctx->kernel_launches[DQ_KERNEL_WHERE_MASKS]++;
-            }
-        }
-        // resolve slot descriptors
-        for (int s = 0; s < nslots; ++s) {
-            SlotDesc& sd = slots[s];
-            const int w = (int)(intptr_t)sd.where_t - 1;
-            sd.where_t = w >= 0 ? pt[w] : nullptr;
-            sd.where_nn = w >= 0 ? pn[w] : nullptr;
-            if (sd.kind == SK_VALUES) {
-                for (int k = 0; k < sd.ncols; ++k) {
-                    const int c = (int)(intptr_t)sd.col[k].values;
-                    sd.col[k].values = dval[c];
-                    sd.col[k].validity = (const uint64_t*)dvalid[c];
-                    sd.col[k].spark_type = columns[c].spark_type;
-                    sd.col[k].elem = elem_of(columns[c].spark_type);
-                    const auto& sm = slot_masks[2 * s + k];
-                    if (sm.first >= 0) sd.col[k].validity = wmask[sm.first][sm.second];  // valid & where TRUE
-                }
-                sd.wout = slot_producer_of[s] >= 0 ? wodev[slot_producer_of[s]] : nullptr;
-            } else {
-                const int tag = (int)sd.col[0].flags;
-                const int ref = (int)(intptr_t)sd.col[0].values;
-                memset(&sd.col[0], 0, sizeof(ColDesc));
-                sd.col[0].hll_slot = -1;
-                sd.ncols = 1;
-                if (tag == 1) sd.bits_valid = (const uint64_t*)dvalid[ref];
-                if (tag == 2) { sd.pred_t = pt[ref]; sd.pred_nn = pn[ref]; }
-            }
-        }
-        int rc = nslots ? upload(dslots, slots.data(), sizeof(SlotDesc) * nslots) : DQ_OK;
-        if (rc) return rc;
-        rc = upload(dops, opmap.data(), sizeof(OpMap) * nops);
-        if (rc) return rc;
-        if (nslots) {
-            std::vector<int32_t> order;
-            for (const Group& g : groups) order.insert(order.end(), g.slots.begin(), g.slots.end());
-            rc = upload(dgroups, order.data(), sizeof(int32_t) * order.size());
-            if (rc) return rc;
-            rc = upload(dslot_nb, slot_nblocks.data(), sizeof(int32_t) * slot_nblocks.size());
-            if (rc) return rc;
-        }
-        if (nsslots) {
-            for (StrSlot& ss : sslots) {
-                const int c = (int)(intptr_t)ss.values;
-                const int w = (int)(intptr_t)ss.where_t - 1;
-                ss.values = dval[c];
-                ss.data = (const uint8_t*)dval[c];
-                ss.offsets = (const int32_t*)doffs[c];
-                ss.validity = (const uint64_t*)dvalid[c];
-                ss.where_t = w >= 0 ? pt[w] : nullptr;
-            }
-            rc = upload(dsslots, sslots.data(), sizeof(StrSlot) * nsslots);
-            if (rc) return rc;
-        }
-        // the scan launches: in order on the ctx stream, or one stream each (fork / join) when concurrent
-        int used_side = 0;
-        auto launch_stream = [&](int i) -> hipStream_t {
-            if (!concurrent || i == 0) return ctx->stream;
-            const int j = (i - 1) % dq_ctx::kSide;
-            used_side = std::max(used_side, j + 1);
-            return ctx->side[j];
-        };
-        int li = 0;
-        size_t goff = 0;
-        size_t gi = 0;
-        auto launch_group = [&](const Group& g, hipStream_t st) -> int {
-            if (launch_scan_group(g.kind, g.P, g.nc, g.f0, g.f1, g.heavy, dslots, dgroups + goff, (int)g.slots.size(), nrows,
-                                  ntiles, gstride, g.grid, partials, hllp, st) != 0)
-                return fail(ctx, DQ_ERR_DEVICE, "scan launch failed for shape (%d,%d,%d)", g.kind, g.P, g.nc);
-            DQ_HIP(ctx, hipGetLastError());
-            ctx->kernel_launches[scan_kernel_family(g.kind, g.P, g.nc, g.heavy)]++;
-            goff += g.slots.size();
-            return DQ_OK;
-        };
-        // `where` producers first, on the ctx stream: every other launch reads their masks
-        for (; gi < groups.size() && groups[gi].heavy == 3; ++gi) {
-            rc = launch_group(groups[gi], ctx->stream);
-            if (rc) return rc;
-        }
-        if (concurrent) {
-            DQ_HIP(ctx, hipEventRecord(ctx->fork_ev, ctx->stream));
-            for (int j = 0; j < std::min(nlaunch - 1, dq_ctx::kSide); ++j)
-                DQ_HIP(ctx, hipStreamWaitEvent(ctx->side[j], ctx->fork_ev, 0));
-        }
-        for (; gi < groups.size(); ++gi) {
-            rc = launch_group(groups[gi], launch_stream(li++));
-            if (rc) return rc;
-        }
-        if (nsslots) {
-            launch_string_scan(dsslots, nsslots, nrows, sgrid, gstride, spartials, hllp, launch_stream(li++));
-            DQ_HIP(ctx, hipGetLastError());
-            ctx->kernel_launches[DQ_KERNEL_STRINGS]++;
-        }
-        for (int j = 0; j < used_side; ++j) {
-            DQ_HIP(ctx, hipEventRecord(ctx->join_ev[j], ctx->side[j]));
-            DQ_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->join_ev[j], 0));
-        }
-        if (ndslots) {
-            for (D128Slot& ds : dslots128) {
-                const int c = (int)(intptr_t)ds.values;
-                const int w = (int)(intptr_t)ds.where_t - 1;
-                ds.values = dval[c];
-                ds.validity = (const uint64_t*)dvalid[c];
-                ds.where_t = w >= 0 ? pt[w] : nullptr;
-                ds.where_nn = w >= 0 ? pn[w] : nullptr;
-            }
-            rc = upload(ddslots, dslots128.data(), sizeof(D128Slot) * ndslots);
-            if (rc) return rc;
-            launch_decimal128_scan(ddslots, ndslots, nrows, dgrid, gstride, dpartials, hllp, ctx->stream);
-            DQ_HIP(ctx, hipGetLastError());
-            ctx->kernel_launches[DQ_KERNEL_DECIMAL128]++;
-        }
-        if (nslots) {
-            launch_reduce_partials(partials, dslot_nb, nslots, gstride, finals, ctx->stream);
-            DQ_HIP(ctx, hipGetLastError());
-        }
-        if (nslots || nsslots || ndslots) ctx->scan_launches++;
-        if (nhll) {
-            rc = upload(dhll_nb, hll_nblocks.data(), sizeof(int32_t) * hll_nblocks.size());
-            if (rc) return rc;
-            launch_reduce_hll(hllp, dhll_nb, nhll, gstride, hllf, ctx->stream);
-            DQ_HIP(ctx, hipGetLastError());
-        }
-        launch_finalize(dops, nops, finals, hllf, dout, ctx->stream);
-        DQ_HIP(ctx, hipGetLastError());
-        if (!sopmap.empty()) {
-            rc = upload(dsops, sopmap.data(), sizeof(StrOpMap) * sopmap.size());
-            if (rc) return rc;
-            launch_finalize_strings(dsops, (int)sopmap.size(), spartials, sgrid, gstride, nrows, dout, ctx->stream);
-            DQ_HIP(ctx, hipGetLastError());
-        }
-        if (!dopmap.empty()) {
-            rc = upload(ddops, dopmap.data(), sizeof(D128OpMap) * dopmap.size());
-            if (rc) return rc;
-            launch_finalize_decimal128(ddslots, ndslots, ddops, (int)dopmap.size(), dpartials, dgrid, gstride, nrows, dout,
-                                       ctx->stream);
-            DQ_HIP(ctx, hipGetLastError());
-        }
-        if (any_status) {
-            // a row that exhausted the backtracking budget, or whose string the device cannot convert to DOUBLE
-            // exactly, fails the batch (never a silent count)
-            int32_t* hs = (int32_t*)hb.take(sizeof(int32_t) * std::max(npreds, 1), 16);
-            DQ_HIP(ctx, hipMemcpyAsync(hs, rx_status, sizeof(int32_t) * std::max(npreds, 1), hipMemcpyDeviceToHost, ctx->stream));
-            DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            for (int p = 0; p < npreds; ++p)
-                if (pred_pass[p] && (hs[p] & 1))
-                    return fail(ctx, DQ_ERR_UNSUPPORTED, "predicate %d: regex backtracking limit exceeded", p);
-            for (int p = 0; p < npreds; ++p)
-                if (pred_pass[p] && hs[p])
-                    return fail(ctx, DQ_ERR_UNSUPPORTED,
-                                "predicate %d: a string needs Double.parseDouble's arbitrary-precision path "
-                                "(hexadecimal literal, or > 19 significant digits on a rounding boundary)", p);
-        }
-        if (!(flags & DQ_SCAN_OUT_DEVICE)) {
-            void* h = hb.take(sizeof(dq_state) * nops, 16);
-            DQ_HIP(ctx, hipMemcpyAsync(h, dout, sizeof(dq_state) * nops, hipMemcpyDeviceToHost, ctx->stream));
-            DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            memcpy(out, h, sizeof(dq_state) * nops);
-        } else {
-            // Host columns were staged into the arena: keep them alive until the kernels finish.
-            bool staged = false;
-            for (int c = 0; c < ncols; ++c) staged |= col_used[c] && !(columns[c].flags & DQ_COL_DEVICE);
-            if (staged) DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        }
-    }
-    return DQ_OK;
+    if ((rc = stage_columns(sc))) return rc;
+    // The pinned buffer may still be read by a previous call's async copies: wait for them.
+    DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    Stager up{ctx};
+    if ((rc = run_predicates(sc, up))) return rc;
+    if ((rc = upload_descriptors(sc, up))) return rc;
+    if ((rc = launch_scans(sc, up))) return rc;
+    dq_state* dout = (flags & DQ_SCAN_OUT_DEVICE) ? out : sc.at<dq_state>(sc.L.out);
+    if ((rc = reduce_and_finalize(sc, up, dout))) return rc;
+    return read_back(sc, up, dout, out, flags);
 }
 
 // Host columns streamed through HBM in row chunks (tables larger than HBM, or host-resident batches): the copy
@@ -1833,71 +1186,17 @@ int check_dict_column(dq_ctx* ctx, const dq_dict_column& d, int64_t nrows, int w
     return DQ_OK;
 }
 
-// Pinned staging of one call's uploads (the buffer is free: the caller synchronised the stream).
-struct Stager {
-    dq_ctx* ctx;
-    Bump hb;
-    int upload(void* dst, const void* src, size_t n) {
-        if (!n) return DQ_OK;
-        void* h = hb.take(n, 16);
-        memcpy(h, src, n);
-        DQ_HIP(ctx, hipMemcpyAsync(dst, h, n, hipMemcpyHostToDevice, ctx->stream));
-        return DQ_OK;
-    }
-};
-
-size_t pred_stage_bytes(const dq_predicate& pr) {
-    return sizeof(PredProgram) + sizeof(int32_t) * (size_t)pr.code_len + sizeof(dq_const) * (size_t)std::max(pr.n_consts, 1) +
-           (size_t)std::max<int64_t>(pr.strings_len, 1) + 1024;
-}
-
-// One predicate over `columns` (pcols_dev: their PredColumn records on the device, pc: the same on the host) into TRUE /
-// NOT-NULL bitmaps of `pwords` words, by the kernels dq_scan evaluates predicates with. *status (device, zeroed) is
-// set by a row the device cannot evaluate (regex backtracking budget, inexact string -> double).
-int eval_predicate_bits(dq_ctx* ctx, const dq_predicate& pr, const dq_column* columns, int ncols, const PredColumn* pc,
-                        const PredColumn* pcols_dev, int64_t nrows, int64_t pwords, uint64_t* pt, uint64_t* pn,
-                        int32_t* status, ScratchBuffers& buf, Stager& up) {
-    if (pr.code_len < 2 || (pr.code_len & 1) || !pr.code) return fail(ctx, DQ_ERR_PREDICATE, "empty predicate program");
-    for (int k = 0; k + 1 < pr.code_len; k += 2) {
-        const int a = pr.code[k + 1];
-        if (pr.code[k] == DQ_P_COL && (a < 0 || a >= ncols))
-            return fail(ctx, DQ_ERR_PREDICATE, "predicate reads column %d of %d", a, ncols);
-        if ((pr.code[k] == DQ_P_CONST || pr.code[k] == DQ_P_REGEX || pr.code[k] == DQ_P_RLIKE || pr.code[k] == DQ_P_LIKE) &&
-            (a < 0 || a >= pr.n_consts))
-            return fail(ctx, DQ_ERR_PREDICATE, "predicate reads constant %d of %d", a, pr.n_consts);
-    }
-    void *dcode = nullptr, *dconst = nullptr, *dstr = nullptr, *dprog = nullptr;
-    DQ_HIP(ctx, buf.alloc(&dcode, sizeof(int32_t) * (size_t)pr.code_len));
-    DQ_HIP(ctx, buf.alloc(&dconst, sizeof(dq_const) * (size_t)std::max(pr.n_consts, 1)));
-    DQ_HIP(ctx, buf.alloc(&dstr, (size_t)std::max<int64_t>(pr.strings_len, 1) + 16));
-    DQ_HIP(ctx, buf.alloc(&dprog, sizeof(PredProgram)));
-    int rc = up.upload(dcode, pr.code, sizeof(int32_t) * (size_t)pr.code_len);
-    if (rc) return rc;
-    if (pr.n_consts > 0 && (rc = up.upload(dconst, pr.consts, sizeof(dq_const) * (size_t)pr.n_consts))) return rc;
-    if (pr.strings_len > 0 && (rc = up.upload(dstr, pr.strings, (size_t)pr.strings_len))) return rc;
-    PredProgram pg;
-    pg.code = (const int32_t*)dcode;
-    pg.consts = (const dq_const*)dconst;
-    pg.strings = (const uint8_t*)dstr;
-    pg.code_len = pr.code_len;
-    pg.n_consts = pr.n_consts;
-    if ((rc = up.upload(dprog, &pg, sizeof(pg)))) return rc;
-    if (pr.code_len == 4 && pr.code[0] == DQ_P_COL && pr.code[2] == DQ_P_REGEX) {
-        const dq_const& k = pr.consts[pr.code[3]];
-        launch_regex(pc[pr.code[1]], (const int32_t*)((const uint8_t*)dstr + k.str_offset), nrows, pwords, pt, pn, status,
-                     ctx->stream);
-        ctx->kernel_launches[DQ_KERNEL_REGEX]++;
-    } else if (PredSimple ps; !pred_vm_forced() && compile_simple_predicate(pr, columns, ncols, ps)) {
-        launch_pred_simple(ps, pcols_dev, nrows, pwords, pt, pn, ctx->stream);
-        ctx->kernel_launches[DQ_KERNEL_PRED_SIMPLE]++;
-    } else {
-        bool rx = false;
-        for (int k = 0; k + 1 < pr.code_len; k += 2) rx |= pr.code[k] == DQ_P_RLIKE;
-        launch_predicate((const PredProgram*)dprog, rx, status, pcols_dev, nrows, pwords, pt, pn, ctx->stream);
-        ctx->kernel_launches[DQ_KERNEL_PRED_VM]++;
-    }
-    DQ_HIP(ctx, hipGetLastError());
-    return DQ_OK;
+// One validated predicate of dq_dict_scan: its program pieces in per-call scratch, then the stage dq_scan uses.
+int dict_predicate(dq_ctx* ctx, Stager& up, ScratchBuffers& buf, const dq_predicate& pr, const dq_column* columns, int ncols,
+                   const PredColumn* pc, const PredColumn* pcols_dev, int64_t nrows, uint64_t* pt, uint64_t* pn, int32_t* status) {
+    PredDevice d{};
+    DQ_HIP(ctx, buf.alloc(&d.code, sizeof(int32_t) * (size_t)pr.code_len));
+    DQ_HIP(ctx, buf.alloc(&d.consts, sizeof(dq_const) * (size_t)std::max(pr.n_consts, 1)));
+    DQ_HIP(ctx, buf.alloc(&d.strings, (size_t)std::max<int64_t>(pr.strings_len, 1) + 16));
+    DQ_HIP(ctx, buf.alloc(&d.prog, sizeof(PredProgram)));
+    bool may_set_status;  // every status word of the call is read back
+    return run_predicate(ctx, up, pr, columns, ncols, pc, pcols_dev, d, nrows, padded_words_for(nrows), pt, pn, status,
+                         pred_vm_forced(), &may_set_status);
 }
 
 void fill_dict_slot(DictSlot& s, const dq_dict_column& d) {
@@ -2030,6 +1329,25 @@ int dq_dict_scan(dq_ctx* ctx, const dq_column* columns, int ncols, const dq_dict
             columns[c].spark_type == DQ_TYPE_DECIMAL128)
             return fail(ctx, DQ_ERR_UNSUPPORTED, "dq_dict_scan: column %d of a where must be a device column of the batch's rows", c);
     }
+    // every program as dq_scan validates it, before any launch: the filters over the plain columns, each Compliance
+    // predicate rewritten to read column 0 = its slot's dictionary
+    std::string why;
+    for (int p = 0; p < npreds; ++p) {
+        if (!where_used[p]) continue;
+        const int rc = validate_predicate(preds[p], columns, ncols, &why);
+        if (rc) return fail(ctx, rc, "dq_dict_scan: predicate %d: %s", p, why.c_str());
+    }
+    std::vector<std::vector<int32_t>> pop_code(npops);
+    for (int q = 0; q < npops; ++q) {
+        const dq_predicate& src = preds[pop_pred[q]];
+        if (src.code && src.code_len > 0) pop_code[q].assign(src.code, src.code + src.code_len);
+        for (size_t k = 0; k + 1 < pop_code[q].size(); k += 2)
+            if (pop_code[q][k] == DQ_P_COL) pop_code[q][k + 1] = 0;
+        dq_predicate pr = src;
+        pr.code = src.code ? pop_code[q].data() : nullptr;
+        const int rc = validate_predicate(pr, &dicts[slot_dict[pop_slot[q]]].dictionary, 1, &why);
+        if (rc) return fail(ctx, rc, "dq_dict_scan: predicate %d: %s", pop_pred[q], why.c_str());
+    }
     DQ_HIP(ctx, hipSetDevice(ctx->device));
     const int grid = dict_counts_grid(ctx->cus, nrows);
     // ---- device buffers --------------------------------------------------------------------------------------
@@ -2080,8 +1398,7 @@ int dq_dict_scan(dq_ctx* ctx, const dq_column* columns, int ncols, const dq_dict
     int rc = ensure_pinned(ctx, pin);
     if (rc) return rc;
     DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the pinned buffer may still feed a previous call's copies
-    Stager up{ctx, Bump()};
-    up.hb.base = ctx->pinned;
+    Stager up{ctx};
     DQ_HIP(ctx, hipMemsetAsync(zero, 0, zwords * 8, ctx->stream));
     DQ_HIP(ctx, hipMemsetAsync(status, 0, sizeof(int32_t) * nstatus, ctx->stream));
     // ---- the where bitmaps over the plain columns ----------------------------------------------------------------
@@ -2089,12 +1406,7 @@ int dq_dict_scan(dq_ctx* ctx, const dq_column* columns, int ncols, const dq_dict
     memset(pc.data(), 0, sizeof(PredColumn) * pc.size());
     for (int c = 0; c < ncols; ++c) {
         if (!(columns[c].flags & DQ_COL_DEVICE)) continue;  // unread (checked above)
-        pc[c].values = columns[c].values;
-        pc[c].validity = (const uint64_t*)columns[c].validity;
-        pc[c].offsets = columns[c].offsets;
-        pc[c].spark_type = columns[c].spark_type;
-        pc[c].elem = elem_of(columns[c].spark_type);
-        pc[c].decimal_scale = columns[c].decimal_scale;
+        pc[c] = pred_column(columns[c], columns[c].values, columns[c].validity, columns[c].offsets);
     }
     const int pc0 = std::max(ncols, 1);
     for (int q = 0; q < npops; ++q) {  // each predicate op's single column: its slot's dictionary
@@ -2108,7 +1420,7 @@ int dq_dict_scan(dq_ctx* ctx, const dq_column* columns, int ncols, const dq_dict
     if ((rc = up.upload(pcols, pc.data(), sizeof(PredColumn) * pc.size()))) return rc;
     for (int p = 0; p < npreds; ++p) {
         if (!where_used[p]) continue;
-        rc = eval_predicate_bits(ctx, preds[p], columns, ncols, pc.data(), pcols, nrows, pwords, wt[p], wn[p], status + p, buf, up);
+        rc = dict_predicate(ctx, up, buf, preds[p], columns, ncols, pc.data(), pcols, nrows, wt[p], wn[p], status + p);
         if (rc) return rc;
     }
     // ---- the per-row pass: every slot in one launch --------------------------------------------------------------
@@ -2131,16 +1443,11 @@ int dq_dict_scan(dq_ctx* ctx, const dq_column* columns, int ncols, const dq_dict
     // ---- per entry: predicates over the dictionaries, then the fold ----------------------------------------------
     std::vector<DictPredOp> pops(std::max(npops, 1));
     for (int q = 0; q < npops; ++q) {
-        const dq_predicate& src = preds[pop_pred[q]];
-        std::vector<int32_t> code(src.code, src.code + std::max(src.code_len, 0));
-        for (size_t k = 0; k + 1 < code.size(); k += 2)
-            if (code[k] == DQ_P_COL) code[k + 1] = 0;  // the dictionary column
-        dq_predicate pr = src;
-        pr.code = code.data();
+        dq_predicate pr = preds[pop_pred[q]];
+        pr.code = pop_code[q].data();  // reads column 0: the dictionary
         const dq_column& e = dicts[slot_dict[pop_slot[q]]].dictionary;
-        const int64_t ne = e.length;
-        rc = eval_predicate_bits(ctx, pr, &e, 1, pc.data() + pc0 + q, pcols + pc0 + q, ne, padded_words_for(ne), pt[q], pn[q],
-                                 status + std::max(npreds, 1) + q, buf, up);
+        rc = dict_predicate(ctx, up, buf, pr, &e, 1, pc.data() + pc0 + q, pcols + pc0 + q, e.length, pt[q], pn[q],
+                            status + std::max(npreds, 1) + q);
         if (rc) return rc;
         pops[q].pred_t = pt[q];
         pops[q].pred_nn = pn[q];
@@ -2158,11 +1465,13 @@ int dq_dict_scan(dq_ctx* ctx, const dq_column* columns, int ncols, const dq_dict
     launch_dict_finalize(dslots, dops, nops, nrows, dout, ctx->stream);
     DQ_HIP(ctx, hipGetLastError());
     // ---- results ---------------------------------------------------------------------------------------------
-    dq_state* hout = (dq_state*)up.hb.take(sizeof(dq_state) * nops, 16);
-    int32_t* hstatus = (int32_t*)up.hb.take(sizeof(int32_t) * nstatus, 16);
-    int64_t* hstats = (int64_t*)up.hb.take(sizeof(int64_t) * DS_COUNT * nslots, 16);
-    DQ_HIP(ctx, hipMemcpyAsync(hout, dout, sizeof(dq_state) * nops, hipMemcpyDeviceToHost, ctx->stream));
-    DQ_HIP(ctx, hipMemcpyAsync(hstatus, status, sizeof(int32_t) * nstatus, hipMemcpyDeviceToHost, ctx->stream));
+    void *hout_ = nullptr, *hstatus_ = nullptr;
+    if ((rc = up.download(&hout_, dout, sizeof(dq_state) * nops))) return rc;
+    if ((rc = up.download(&hstatus_, status, sizeof(int32_t) * nstatus))) return rc;
+    const dq_state* hout = (const dq_state*)hout_;
+    const int32_t* hstatus = (const int32_t*)hstatus_;
+    int64_t* hstats = (int64_t*)up.take(sizeof(int64_t) * DS_COUNT * nslots);
+    if (!hstats) return fail(ctx, DQ_ERR_DEVICE, "dq_dict_scan: pinned staging exhausted");
     for (int s = 0; s < nslots; ++s)
         DQ_HIP(ctx, hipMemcpyAsync(hstats + DS_COUNT * s, slots[s].stats, sizeof(int64_t) * DS_COUNT, hipMemcpyDeviceToHost, ctx->stream));
     DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));

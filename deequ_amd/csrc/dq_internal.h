@@ -4,10 +4,21 @@
 // Correlation pair) under one `where` mask, or a bits-only pass over validity/predicate bitmaps
 // (Size(where), Completeness of an otherwise unread column, Compliance). Every op of the batch
 // is answered from the final slot partial it maps to (OpMap), so every column is read once.
+//
+// A call is planned on the host as plain records (ScanPlan, scan_plan.h): a plan slot names its columns, its `where`
+// and its mask assignment by integer index. The device descriptors below (SlotDesc, StrSlot, D128Slot, WhereOut,
+// PredColumn) are built from a plan record and the arena layout only once every device address is known, each by one
+// resolve function of dq_api.cpp that fills a fresh struct; no descriptor field ever holds an index.
+//
+// The layouts up to rows_per_load_of compile without HIP (-DDQ_HOST_ONLY: scan_plan.cpp under the host sanitizers);
+// the context, the scratch helpers and the kernel launchers after them need the HIP runtime.
 #pragma once
 
+#if !defined(DQ_HOST_ONLY)
 #include <hip/hip_runtime.h>
+#endif
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/dq.h"
 
@@ -278,9 +289,27 @@ inline int rows_per_load_of(int e) {
     int s = elem_size(e);
     return s == 8 ? 2 : (s == 4 ? 4 : 8);
 }
+// Words of a TRUE / NOT-NULL bitmap or a consumer mask: whole tiles, at least one.
+inline int64_t padded_words_for(int64_t nrows) {
+    const int64_t tiles = nrows > kTileRows ? (nrows + kTileRows - 1) / kTileRows : 1;
+    return tiles * (kTileRows / 64);
+}
+
+namespace rx {
+// Host check of a compiled regex image (rx_engine.h) of `len` bytes before it is uploaded: the header's counts add up
+// to exactly its length, so the kernels read nothing past it.
+static inline bool rx_image_ok(const void* image, int64_t len) {
+    if ((len & 3) || len < 32) return false;
+    int32_t h[4];
+    memcpy(h, image, sizeof(h));
+    return h[1] > 0 && h[2] >= 0 && h[3] >= 0 &&
+           len == 4 * (8 + 3 * (int64_t)h[1] + 2 * (int64_t)h[2] + 2 * (int64_t)h[3]);
+}
+}  // namespace rx
 
 }  // namespace dq
 
+#if !defined(DQ_HOST_ONLY)
 #ifdef __cplusplus
 #include <algorithm>
 #include <map>
@@ -453,3 +482,4 @@ void launch_synth_validity(uint64_t seed, int64_t row0, int64_t nrows, int permi
                            hipStream_t s);
 
 }  // namespace dq
+#endif  // !DQ_HOST_ONLY

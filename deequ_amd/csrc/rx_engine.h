@@ -430,16 +430,6 @@ __device__ __forceinline__ RxProg rx_program(const int32_t* image) {
     return p;
 }
 
-// Host check of an image of `len` bytes before it is uploaded: the header's counts add up to exactly its length, so
-// the kernels read nothing past it.
-static inline bool rx_image_ok(const void* image, int64_t len) {
-    if ((len & 3) || len < 32) return false;
-    int32_t h[4];
-    memcpy(h, image, sizeof(h));
-    return h[1] > 0 && h[2] >= 0 && h[3] >= 0 &&
-           len == 4 * (8 + 3 * (int64_t)h[1] + 2 * (int64_t)h[2] + 2 * (int64_t)h[3]);
-}
-
 // Matcher.find(): the first start position (code point boundaries) with a match. Returns that match's end with its
 // start in `start` (an empty match has end == start), -1 = no match, -2 = resource limit.
 // `inline` like rx_match_at, not __forceinline__: the compiler inlines both into the kernels either way, but forcing

@@ -8,7 +8,9 @@ OUT=../../tools/ab
 mkdir -p $OUT/$NAME.build
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -Wall -Wno-unused-function"
 objs=""
-for f in dq_api.cpp host_algebra.cpp multi.cpp scan.hip predicate.hip synth.hip freq.hip quantile.hip strings.hip regex.hip kll.hip cast.hip; do
+SRCS=$(sed -n 's/^SRCS := //p' Makefile)  # the library's sources, as the Makefile lists them
+[ -n "$SRCS" ] || { echo "no SRCS in deequ_amd/csrc/Makefile" >&2; exit 1; }
+for f in $SRCS; do
   src=$f
   if [ "$f" = freq.hip ] && [ -n "${FREQ_REV:-}" ]; then git show "$FREQ_REV:deequ_amd/csrc/freq.hip" > _ab_rev_freq.hip; src=_ab_rev_freq.hip; fi
   if [ "$f" = strings.hip ] && [ -n "${STR_REV:-}" ]; then git show "$STR_REV:deequ_amd/csrc/strings.hip" > _ab_rev_strings.hip; src=_ab_rev_strings.hip; fi
