@@ -156,12 +156,19 @@ STATE_ONLY = DoubleMetric(Entity.Dataset, "StateOnly", "*", Success(0.0))
 # ---- Analyzer base classes (A/Analyzer.scala:56-197) ---------------------------------------------
 class Analyzer:
     _fields = ()
+    # The grouping analyzers and ApproxQuantile take `where` as an optional trailing parameter that the reference's
+    # case classes do not have: it is no member of _fields, and key, hash and repr of an analyzer without a filter
+    # are exactly those of the reference's case class (persisted states are named by the repr). With a filter the key
+    # gains it and the repr appends ",Some(<text>)", as the later deequ case classes print it.
+    _trailing_where = False
 
     def _key(self):
         k = self.__dict__.get("_cached_key")  # analyzers are values: fields are not changed after construction
         if k is None:
             k = (type(self).__name__,) + tuple(
                 tuple(v) if isinstance(v, list) else v for v in (getattr(self, f) for f in self._fields))
+            if self._trailing_where and self.where is not None:
+                k += (("where", self.where),)
             self.__dict__["_cached_key"] = k
         return k
 
@@ -184,6 +191,8 @@ class Analyzer:
             elif isinstance(v, float):
                 v = _java_double_to_string(v)  # Scala's Double.toString inside the case-class toString
             args.append(str(v))
+        if self._trailing_where and self.where is not None:
+            args.append("Some(%s)" % self.where)
         return "%s(%s)" % (type(self).__name__, ",".join(args))
 
     def preconditions(self):
@@ -532,11 +541,15 @@ def _quantile_param_checks(quantiles, relativeError):
 
 class ApproxQuantile(ScanShareableAnalyzer):
     """A/ApproxQuantile.scala:44-103. The digest comes from dq_quantile_summary (exact order
-    statistics on the GPU, deequ_amd/quantiles.py); `where` is not supported, as in the reference."""
+    statistics on the GPU, deequ_amd/quantiles.py). `where` (not in the reference snapshot; later deequ releases
+    have it): the quantile of the rows on which the filter is TRUE, read through a filtered view of the column
+    (engine.FilterCache) -- the summary kernels skip NULL cells, so they take no filter."""
     _fields = ("column", "quantile", "relativeError")
+    _trailing_where = True
 
-    def __init__(self, column, quantile, relativeError=0.01):
+    def __init__(self, column, quantile, relativeError=0.01, where=None):
         self.column, self.quantile, self.relativeError = column, float(quantile), float(relativeError)
+        self.where = where
 
     @property
     def _metric_name(self):
@@ -547,7 +560,7 @@ class ApproxQuantile(ScanShareableAnalyzer):
                 Preconditions.isNumeric(self.column)]
 
     def addOps(self, batch):
-        return [batch.add_quantile(self.column, self.relativeError)]
+        return [batch.add_quantile(self.column, self.relativeError, self.where)]
 
     def fromAggregationResult(self, states, ops):
         digest = states.quantiles[ops[0]]
@@ -918,6 +931,8 @@ def computeFrequencies(data, groupingColumns, include_nulls=False):
 
 
 class GroupingAnalyzer(Analyzer):
+    where = None
+
     def groupingColumns(self):
         raise NotImplementedError
 
@@ -926,15 +941,22 @@ class GroupingAnalyzer(Analyzer):
 
 
 class FrequencyBasedAnalyzer(GroupingAnalyzer):
+    """`where` (not in the reference snapshot; later deequ releases have it): the analyzer over the rows on which the
+    filter is TRUE. A dropped row is a row whose key columns are all NULL, which the grouping already drops: the
+    frequencies are built over a filtered view of the key columns (engine.FilterCache), by the same kernels."""
     _fields = ("columns",)
+    _trailing_where = True
 
-    def __init__(self, columns):
+    def __init__(self, columns, where=None):
         self.columns = [columns] if isinstance(columns, str) else list(columns)
+        self.where = where
 
     def groupingColumns(self):
         return self.columns
 
     def computeStateFrom(self, data):
+        if self.where is not None:
+            data = engine.FilterCache().view(data, self.where, self.groupingColumns())
         return computeFrequencies(data, self.groupingColumns())
 
     def preconditions(self):
@@ -1012,8 +1034,8 @@ class Entropy(ScanShareableFrequencyBasedAnalyzer):
     name = "Entropy"
     _fields = ("column",)
 
-    def __init__(self, column):
-        super().__init__([column])
+    def __init__(self, column, where=None):
+        super().__init__([column], where)
         self.column = column
 
     def valueFromSummary(self, s, numRows):

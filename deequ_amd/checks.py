@@ -170,16 +170,22 @@ class Check:
         return self.hasUniqueness([column] + list(columns), is_one)
 
     def hasUniqueness(self, columns, assertion, hint=None):
-        u = A.Uniqueness([columns] if isinstance(columns, str) else list(columns))
-        return self.addConstraint(_named(u, assertion, "UniquenessConstraint(%r)" % u, hint=hint))
+        def mk(where):
+            u = A.Uniqueness([columns] if isinstance(columns, str) else list(columns), where)
+            return _named(u, assertion, "UniquenessConstraint(%r)" % u, hint=hint)
+        return self._filterable(mk)
 
     def hasDistinctness(self, columns, assertion, hint=None):
-        d = A.Distinctness(list(columns))
-        return self.addConstraint(_named(d, assertion, "DistinctnessConstraint(%r)" % d, hint=hint))
+        def mk(where):
+            d = A.Distinctness(list(columns), where)
+            return _named(d, assertion, "DistinctnessConstraint(%r)" % d, hint=hint)
+        return self._filterable(mk)
 
     def hasUniqueValueRatio(self, columns, assertion, hint=None):
-        u = A.UniqueValueRatio(list(columns))
-        return self.addConstraint(_named(u, assertion, "UniqueValueRatioConstraint(%r" % u, hint=hint))
+        def mk(where):
+            u = A.UniqueValueRatio(list(columns), where)
+            return _named(u, assertion, "UniqueValueRatioConstraint(%r" % u, hint=hint)
+        return self._filterable(mk)
 
     def hasNumberOfDistinctValues(self, column, assertion, binningUdf=None,
                                   maxBins=A.Histogram.MaximumAllowedDetailBins, hint=None):
@@ -194,16 +200,22 @@ class Check:
 
     # ---- information ------------------------------------------------------------------------
     def hasEntropy(self, column, assertion, hint=None):
-        e = A.Entropy(column)
-        return self.addConstraint(_named(e, assertion, "EntropyConstraint(%r)" % e, hint=hint))
+        def mk(where):
+            e = A.Entropy(column, where)
+            return _named(e, assertion, "EntropyConstraint(%r)" % e, hint=hint)
+        return self._filterable(mk)
 
     def hasMutualInformation(self, columnA, columnB, assertion, hint=None):
-        m = A.MutualInformation([columnA, columnB])
-        return self.addConstraint(_named(m, assertion, "MutualInformationConstraint(%r)" % m, hint=hint))
+        def mk(where):
+            m = A.MutualInformation([columnA, columnB], where)
+            return _named(m, assertion, "MutualInformationConstraint(%r)" % m, hint=hint)
+        return self._filterable(mk)
 
     def hasApproxQuantile(self, column, quantile, assertion, hint=None):
-        q = A.ApproxQuantile(column, quantile)
-        return self.addConstraint(_named(q, assertion, "ApproxQuantileConstraint(%r)" % q, hint=hint))
+        def mk(where):
+            q = A.ApproxQuantile(column, quantile, where=where)
+            return _named(q, assertion, "ApproxQuantileConstraint(%r)" % q, hint=hint)
+        return self._filterable(mk)
 
     # ---- per-column statistics (filterable) -------------------------------------------------
     def _stat(self, cls, label, column, assertion, hint):

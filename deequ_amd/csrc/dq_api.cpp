@@ -601,9 +601,8 @@ int reduce_and_finalize(ScanCall& sc, Stager& up, dq_state* dout) {
     return DQ_OK;
 }
 
-// The predicates' status words (read only when one may be set), then the states: to `out`, or left at `out` on the
-// device (DQ_SCAN_OUT_DEVICE), where staged host columns must outlive the kernels.
-int read_back(ScanCall& sc, Stager& up, const dq_state* dout, dq_state* out, uint32_t flags) {
+// The predicates' status words, read only when one may be set.
+int check_pred_status(ScanCall& sc, Stager& up) {
     dq_ctx* ctx = sc.ctx;
     int rc;
     if (sc.any_status) {
@@ -622,6 +621,15 @@ int read_back(ScanCall& sc, Stager& up, const dq_state* dout, dq_state* out, uin
                             "predicate %d: a string needs Double.parseDouble's arbitrary-precision path "
                             "(hexadecimal literal, or > 19 significant digits on a rounding boundary)", p);
     }
+    return DQ_OK;
+}
+
+// The status words, then the states: to `out`, or left at `out` on the device (DQ_SCAN_OUT_DEVICE), where staged host
+// columns must outlive the kernels.
+int read_back(ScanCall& sc, Stager& up, const dq_state* dout, dq_state* out, uint32_t flags) {
+    dq_ctx* ctx = sc.ctx;
+    int rc;
+    if ((rc = check_pred_status(sc, up))) return rc;
     if (!(flags & DQ_SCAN_OUT_DEVICE)) {
         void* h = nullptr;
         if ((rc = up.download(&h, dout, sizeof(dq_state) * sc.nops))) return rc;
@@ -936,6 +944,89 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
     dq_state* dout = (flags & DQ_SCAN_OUT_DEVICE) ? out : sc.at<dq_state>(sc.L.out);
     if ((rc = reduce_and_finalize(sc, up, dout))) return rc;
     return read_back(sc, up, dout, out, flags);
+}
+
+// The filter goes through dq_scan's own stages as the `where` of one Size op planned for the bitmap pass (validate,
+// plan, layout, stage_columns, run_predicates: the TRUE bitmap lands in the arena), then one filter_validity_kernel
+// launch (filter.hip) ANDs it into every target's validity. The scan launch itself is never issued.
+int dq_filter_validity(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, const dq_predicate* pred,
+                       const int32_t* target_columns, int ntargets, uint8_t* const* out_validity_dev, int64_t* true_rows) {
+    if (!ctx) return DQ_ERR_INVALID_ARGUMENT;
+    ctx->err.clear();
+    if (!columns || ncols <= 0 || nrows < 0 || !pred || ntargets < 0 || !true_rows ||
+        (ntargets > 0 && (!target_columns || !out_validity_dev)))
+        return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_filter_validity: invalid arguments");
+    *true_rows = 0;
+    if (!ctx->subs.empty()) return fail(ctx, DQ_ERR_UNSUPPORTED, "dq_filter_validity: multi-device contexts are not supported");
+    if (ntargets > kFilterTargets)
+        return fail(ctx, DQ_ERR_UNSUPPORTED, "dq_filter_validity: %d targets, at most %d per call", ntargets, kFilterTargets);
+    for (int j = 0; j < ntargets; ++j) {
+        const int c = target_columns[j];
+        if (c < 0 || c >= ncols) return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_filter_validity: target %d names column %d", j, c);
+        if (columns[c].length != nrows)
+            return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "column %d has %lld rows, batch has %lld", c, (long long)columns[c].length,
+                        (long long)nrows);
+        if (!out_validity_dev[j]) return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_filter_validity: target %d has no output bitmap", j);
+        if (((uintptr_t)out_validity_dev[j] & 7) || ((columns[c].flags & DQ_COL_DEVICE) && ((uintptr_t)columns[c].validity & 7)))
+            return fail(ctx, DQ_ERR_ALIGNMENT, "dq_filter_validity: bitmaps must be 8-B aligned (target %d)", j);
+    }
+    DQ_HIP(ctx, hipSetDevice(ctx->device));
+
+    const dq_op op{DQ_OP_SIZE, {-1, -1}, 0, -1};
+    ScanCall sc{ctx, columns, ncols, nrows, &op, 1, pred, 1};
+    std::string msg;
+    int rc = validate_scan(columns, ncols, nrows, &op, 1, pred, 1, &sc.use, &msg);
+    if (rc) return fail(ctx, rc, "%s", msg.c_str());
+    if (nrows == 0) return DQ_OK;
+    sc.options.where_masks = false;  // the bitmap pass: TRUE / NOT-NULL bitmaps from a predicate launch
+    sc.options.pred_vm = pred_vm_forced();
+    rc = plan_scan(columns, ncols, nrows, &op, 1, pred, 1, sc.use, sc.options, &sc.plan, &msg);
+    if (rc) return fail(ctx, rc, "%s", msg.c_str());
+    if ((rc = scan_geometry(sc))) return rc;
+    sc.L = layout_scan(sc.plan, sc.geo, sc.use, columns, ncols, nrows, 1, pred, 1, true);
+    if ((rc = ensure_arena(ctx, sc.L.arena_bytes))) return rc;
+    if ((rc = ensure_pinned(ctx, sc.L.pinned_bytes + 64))) return rc;  // + the TRUE-row count's read-back
+
+    if ((rc = stage_columns(sc))) return rc;
+    DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the pinned buffer may still be read by a previous call's copies
+    Stager up{ctx};
+    if ((rc = run_predicates(sc, up))) return rc;
+
+    // a host target the predicate does not read: only its bitmap goes to the device
+    ScratchBuffers buf(ctx);
+    const size_t bitmap_bytes = (size_t)(nrows + 7) / 8;
+    FilterTargets ft;
+    memset(&ft, 0, sizeof(ft));
+    ft.ntargets = ntargets;
+    for (int j = 0; j < ntargets; ++j) {
+        const int c = target_columns[j];
+        const dq_column& col = columns[c];
+        ft.out[j] = (uint64_t*)out_validity_dev[j];
+        if ((col.flags & DQ_COL_DEVICE) || sc.use.col_used[c] || !col.validity) {
+            ft.valid[j] = (col.flags & DQ_COL_DEVICE) ? col.validity : (const uint8_t*)sc.valid[c];
+            continue;
+        }
+        void* vd = nullptr;
+        DQ_HIP(ctx, buf.alloc(&vd, align_up(bitmap_bytes, 8) + 8));
+        DQ_HIP(ctx, hipMemcpyAsync(vd, col.validity, bitmap_bytes, hipMemcpyHostToDevice, ctx->stream));
+        ft.valid[j] = (const uint8_t*)vd;
+    }
+    unsigned long long* dcount = nullptr;
+    DQ_HIP(ctx, buf.alloc((void**)&dcount, sizeof(*dcount)));
+    DQ_HIP(ctx, hipMemsetAsync(dcount, 0, sizeof(*dcount), ctx->stream));
+    if (launch_filter_validity(sc.pred_t(0), ft, nrows, dcount, ctx->stream) != 0)
+        return fail(ctx, DQ_ERR_UNSUPPORTED, "dq_filter_validity: more than 2^45 rows in one call (filter in chunks)");
+    DQ_HIP(ctx, hipGetLastError());
+    ctx->kernel_launches[DQ_KERNEL_FILTER_VALIDITY]++;
+    if ((rc = check_pred_status(sc, up))) {
+        (void)hipStreamSynchronize(ctx->stream);  // staged host bitmaps must outlive the kernels
+        return rc;
+    }
+    void* h = nullptr;
+    if ((rc = up.download(&h, dcount, sizeof(*dcount)))) return rc;
+    DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *true_rows = (int64_t) * (const unsigned long long*)h;
+    return DQ_OK;
 }
 
 // Host columns streamed through HBM in row chunks (tables larger than HBM, or host-resident batches): the copy

@@ -261,6 +261,15 @@ struct WhereOut {
     uint64_t* mask[kWhereMasks];          // out: valid & where TRUE, padded bitmap
 };
 
+// dq_filter_validity: the targets of one filter_validity_kernel launch (filter.hip), passed by value.
+constexpr int kFilterTargets = 32;
+struct FilterTargets {
+    int32_t ntargets;
+    int32_t pad;
+    const uint8_t* valid[kFilterTargets];  // target validity, ceil(nrows / 8) readable bytes, 8-B aligned; nullptr = all valid
+    uint64_t* out[kFilterTargets];         // out: TRUE & valid, (nrows + 63) / 64 words
+};
+
 inline int elem_of(int32_t spark_type) {
     switch (spark_type) {
         case DQ_TYPE_BOOLEAN: return ET_U8;
@@ -473,6 +482,10 @@ void launch_finalize_decimal128(const D128Slot* slots, int nslots, const D128OpM
                                 hipStream_t s);
 void launch_regex(const PredColumn& col, const int32_t* image_dev, int64_t nrows, int64_t padded_words,
                   uint64_t* out_t, uint64_t* out_nn, int32_t* status, hipStream_t s);
+// out[j] = true_bits & valid[j] for every target, bits at and past nrows cleared; *true_rows (device, zeroed) += the
+// TRUE rows. Returns non-zero when nrows is 0 or needs more than 2^31 - 1 workgroups.
+int launch_filter_validity(const uint64_t* true_bits, const FilterTargets& targets, int64_t nrows,
+                           unsigned long long* true_rows, hipStream_t s);
 void launch_synth_column(int kind, uint64_t seed, int64_t row0, int64_t nrows, void* out, hipStream_t s);
 void launch_synth_freq_keys(int64_t total, int64_t distinct, int64_t row0, int64_t nrows, int64_t* out, hipStream_t s);
 void launch_synth_string_lengths(int kind, uint64_t seed, int64_t row0, int64_t nrows, int32_t* lens, hipStream_t s);

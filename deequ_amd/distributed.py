@@ -360,6 +360,13 @@ class DistributedAnalysisRunner:
             except UnsupportedOnDevice as e:
                 results[a] = a.toFailureMetric(e)
                 passed.remove(a)
+        # a `where` on a grouping analyzer or ApproxQuantile is evaluated by single-process runs only
+        # (dq_filter_validity): such an analyzer fails alone, on every rank alike
+        for a in list(passed):
+            if getattr(a, "_trailing_where", False) and a.where is not None:
+                results[a] = a.toFailureMetric(UnsupportedOnDevice(
+                    "%r: a `where` on a grouping analyzer or ApproxQuantile is not supported in a distributed run" % (a,)))
+                passed.remove(a)
         kll = [a for a in passed if isinstance(a, KLLSketch)]
         shareable = [a for a in passed if isinstance(a, ScanShareableAnalyzer) and not isinstance(a, KLLSketch)]
         if kll:

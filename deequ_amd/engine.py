@@ -295,6 +295,100 @@ class FrequencyTable:
         return out
 
 
+def _masked_column(col, dev_bitmap, host_bitmap):
+    """`col` with its validity replaced: the same value / offset buffers (no copy), `dev_bitmap` (a torch uint8 tensor
+    in HBM) where the column is device-resident, `host_bitmap` (numpy) where it has host buffers."""
+    from .table import Column, DictColumn
+    if isinstance(col, DictColumn):
+        out = DictColumn(col.name, col.indices, host_bitmap, col.dictionary)
+        if col.dict_device is not None:
+            out.dict_device = dict(col.dict_device, validity=dev_bitmap)
+        return out
+    out = Column(col.name, col.spark_type, col.values, host_bitmap if col.values is not None else None, col.offsets,
+                 col.decimal_precision, col.decimal_scale, length=col.length)
+    out.tz = col.tz
+    if getattr(col, "offsets64", False):
+        out.offsets64 = True
+    if col.device is not None:
+        out.device = dict(col.device, validity=dev_bitmap)
+    return out
+
+
+class FilterCache:
+    """The filtered views of one run: `view(data, where, names)` is a Table of the columns `names` of `data` that
+    holds, for every consumer that skips NULL cells, exactly the rows on which `where` is TRUE -- the same buffers with
+    validity = TRUE(where) & validity (dq_filter_validity: one predicate evaluation and one mask launch for all the
+    columns asked for). The grouping builds drop rows whose key columns are all NULL and the quantile summaries skip
+    NULL cells, so they read the view with no filter argument of their own. Cached by (table, where text): every
+    analyzer of a run that shares the text shares the evaluation. A ChunkedTable gives a ChunkedTable of per-chunk
+    views (each chunk's own bitmaps). `kept_rows` of a view is the number of TRUE rows; `filtered_where` its text (a
+    view asked for the same filter again is returned as it is).
+
+    The text compiles as a Compliance predicate does (the same exceptions); a multi-device context raises
+    UnsupportedOnDevice."""
+
+    def __init__(self):
+        self._lock = threading.Lock()
+        self._entries = {}  # (id(table), where) -> [table (kept alive: the id stays its), {name: column}, kept rows]
+
+    def view(self, data, where, names):
+        from .table import ChunkedTable, Table
+        if getattr(data, "filtered_where", None) == where:
+            return data
+        if isinstance(data, ChunkedTable):
+            out = ChunkedTable([self.view(chunk, where, names) for chunk in data.chunks])
+            out.filtered_where = where
+            out.kept_rows = sum(c.kept_rows for c in out.chunks)
+            return out
+        names = list(dict.fromkeys(names))
+        with self._lock:
+            entry = self._entries.setdefault((id(data), where), [data, {}, 0])
+            missing = [n for n in names if n not in entry[1]]
+            if missing or not entry[1]:
+                cols, kept = self._evaluate(data, where, missing)
+                entry[1].update(cols)
+                entry[2] = kept
+            out = Table([entry[1][n] for n in names])
+            if not names:
+                out.nrows = data.nrows
+            out.filtered_where = where
+            out.kept_rows = entry[2]
+            return out
+
+    @staticmethod
+    def _evaluate(data, where, names):
+        """{name: masked column} for `names`, and the TRUE rows."""
+        import torch
+        from .metrics import NoSuchColumnException, UnsupportedOnDevice
+        from .runners import ScanBatch
+        from .table import DictColumn
+        context = ctx()
+        batch = ScanBatch(data)
+        p = batch.predicate(where)  # compiled and checked as a Compliance predicate is
+        pred = batch.preds[p]
+        for n in names:
+            if n not in batch.col_index:
+                raise NoSuchColumnException("Input data does not include column %s!" % n)
+        if getattr(context, "multi", False):
+            raise UnsupportedOnDevice("a `where` on a grouping analyzer or ApproxQuantile needs a single-device context")
+        cols = batch.native_columns(batch._pred_columns(p))  # a kept dictionary column decodes only if the filter reads it
+        dev = torch.device("cuda", context.device)
+        nwords = (data.nrows + 63) // 64
+        kept, out = 0, {}
+        for at in range(0, max(len(names), 1), context.FILTER_TARGETS):
+            part = names[at:at + context.FILTER_TARGETS]
+            bitmaps = [torch.zeros(max(nwords, 1) * 8, dtype=torch.uint8, device=dev) if data.nrows == 0 else
+                       torch.empty(nwords * 8, dtype=torch.uint8, device=dev) for _ in part]
+            kept = context.filter_validity(cols, data.nrows, pred.to_native(), [batch.col_index[n] for n in part],
+                                           [b.data_ptr() for b in bitmaps])
+            for n, b in zip(part, bitmaps):
+                col = data[n]
+                # copied back (n / 8 bytes) where the column has a host side: its cells are then read on the host
+                host_side = isinstance(col, DictColumn) or col.values is not None
+                out[n] = _masked_column(col, b, b.cpu().numpy() if host_side else None)
+        return out, kept
+
+
 def frequencies(table, key_columns, include_nulls=False, weights=None):
     """dq_frequencies over `key_columns` of `table`; with `weights` (int64 numpy array, one count per row) each row
     stands for that many rows (dq_frequencies_ex: the pre-aggregated groups of other shards)."""

@@ -61,7 +61,8 @@ HLL_NUM_WORDS = 52
 FREQ_PATHS = ("fast", "fast_narrow", "fast_done", "exact", "partitioned", "sorted", "small", "small_optimistic", "fast_spill",
               "split_buckets", "long_tuples")
 SCAN_KERNELS = ("striped", "striped_heavy", "heavy8", "heavy8_full", "bits", "pred_simple", "pred_vm", "regex",
-                "strings", "where_fused", "where_masks", "decimal128", "dict_counts", "dict_fold", "dict_decode")
+                "strings", "where_fused", "where_masks", "decimal128", "dict_counts", "dict_fold", "dict_decode",
+                "filter_validity")
 
 # Every symbol include/dq.h declares (checked by tests/test_native_abi.py).
 EXPORTED_SYMBOLS = (
@@ -75,7 +76,7 @@ EXPORTED_SYMBOLS = (
     "dq_kll_merge_states", "dq_scratch_trim", "dq_frequencies_parts", "dq_set_priority",
     "dq_schema_validate", "dq_schema_launch_count", "dq_gather_rows", "dq_parse_int32", "dq_parse_decimal",
     "dq_parse_timestamp", "dq_split_rows", "dq_split_row_is_test", "dq_dec128_to_double",
-    "dq_dict_scan", "dq_dict_counts", "dq_dict_decode",
+    "dq_dict_scan", "dq_dict_counts", "dq_dict_decode", "dq_filter_validity",
 )
 
 
@@ -333,6 +334,8 @@ def load_library(path=None):
                                      c_int, c_void_p]),
             "dq_dict_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
             "dq_dict_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+            "dq_filter_validity": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p,
+                                           c_void_p]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name)
@@ -670,6 +673,21 @@ class Context:
                                            ctypes.c_void_p(offsets_ptr) if offsets_ptr else None, ctypes.byref(nbytes)),
                    "dq_gather_rows")
         return int(nbytes.value)
+
+    FILTER_TARGETS = 32  # targets of one dq_filter_validity call (dq_internal.h kFilterTargets)
+
+    def filter_validity(self, columns, nrows, pred, targets, out_ptrs):
+        """dq_filter_validity: `pred` (a DqPredicate) over `columns`, ANDed into the validity of the columns indexed by
+        `targets`, into the device bitmaps `out_ptrs` ((nrows + 63) // 64 words each); returns the TRUE rows."""
+        self._after_torch_stream()
+        col_arr = (DqColumn * max(len(columns), 1))(*columns)
+        tgt = np.asarray(targets, dtype=np.int32)
+        outs = (ctypes.c_void_p * max(len(out_ptrs), 1))(*[int(p) for p in out_ptrs])
+        true_rows = ctypes.c_int64(0)
+        self.check(self.lib.dq_filter_validity(self.handle, col_arr, len(columns), int(nrows), ctypes.byref(pred),
+                                               tgt.ctypes.data, len(tgt), outs, ctypes.byref(true_rows)),
+                   "dq_filter_validity")
+        return int(true_rows.value)
 
     def split_rows(self, nrows, row0, seed, test_ratio, train_ptr, test_ptr):
         """dq_split_rows into two device bitmaps (either pointer may be None); returns (num_train, num_test)."""

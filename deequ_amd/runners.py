@@ -127,8 +127,9 @@ class ScanBatch:
     ApproxQuantile(s) register quantile requests, one dq_quantile_summary per (column, relativeError)
     after the fused pass (they share one digest, as Spark computes identical digests)."""
 
-    def __init__(self, data):
+    def __init__(self, data, filters=None):
         self.data = data
+        self.filters = filters  # the run's engine.FilterCache (filtered ApproxQuantile requests); made on first use
         self.names = list(data.columns)
         self.col_index = {n: i for i, n in enumerate(self.names)}
         self.preds = []
@@ -206,16 +207,27 @@ class ScanBatch:
             self.op_index[key] = len(self.ops) - 1
         return self.op_index[key]
 
-    def add_quantile(self, column, relativeError):
+    def add_quantile(self, column, relativeError, where=None):
         if column not in self.col_index:
             from .metrics import NoSuchColumnException
             raise NoSuchColumnException("Input data does not include column %s!" % column)
         reject_wide_decimals(self.data, [column], "ApproxQuantile")
-        key = (column, float(relativeError))
+        key = (column, float(relativeError)) if where is None else (column, float(relativeError), where)
         if key not in self.quantile_index:
+            if where is not None:  # evaluated now (once per text and run): a filter that fails fails this analyzer
+                if self.filters is None:
+                    self.filters = engine.FilterCache()
+                self.filters.view(self.data, where, [column])
             self.quantile_reqs.append(key)
             self.quantile_index[key] = len(self.quantile_reqs) - 1
         return self.quantile_index[key]
+
+    def _quantile_source(self, req):
+        """(column, rows that can take part) of one quantile request: the filtered view's column under a `where`."""
+        if len(req) == 2:
+            return self.data[req[0]], self.data.nrows
+        view = self.filters.view(self.data, req[2], [req[0]])
+        return view[req[0]], view.kept_rows
 
     def native_columns(self, decoded=None):
         """The batch's columns for the C-ABI. A dictionary-encoded column (DictColumn) goes as its decoded STRING
@@ -315,11 +327,15 @@ class ScanBatch:
             from .quantiles import PercentileDigest, DEFAULT_HEAD_SIZE
             # below the head-buffer size Spark's digest is a function of the sorted values: get all of them (rank
             # spacing 1) and rebuild Spark's own summary; above it, a bounded summary. Every request in one call.
-            small = self.data.nrows < DEFAULT_HEAD_SIZE
+            # (Under a `where` the rows are the filter's TRUE rows, as over a table of exactly those rows.)
+            sources = [self._quantile_source(req) for req in self.quantile_reqs]
+            smalls = [rows < DEFAULT_HEAD_SIZE for _, rows in sources]
             got = engine.ctx().quantile_summaries(
-                [(self.data[column].native_parts(), 0.0 if small else rel) for column, rel in self.quantile_reqs])
+                [(col.native_parts(), 0.0 if small else req[1])
+                 for req, (col, _), small in zip(self.quantile_reqs, sources, smalls)])
             res.quantiles = []
-            for (column, rel), (vals, ranks, n) in zip(self.quantile_reqs, got):
+            for req, small, (vals, ranks, n) in zip(self.quantile_reqs, smalls, got):
+                rel = req[1]
                 if small:
                     res.quantiles.append(PercentileDigest.spark_single_partition(rel, vals))
                 else:
@@ -486,6 +502,33 @@ class KLLRunner:
         return AnalyzerContext(results)
 
 
+def _grouping_key(a):
+    """What grouping analyzers share one frequency table by: their sorted columns and their `where`."""
+    return tuple(sorted(a.groupingColumns())), a.where
+
+
+def _prepare_filters(data, analyzers, filters):
+    """Evaluates every distinct `where` of the grouping analyzers and ApproxQuantiles among `analyzers` once, on this
+    thread's context, for all the columns read under it (one predicate pass and one mask launch per text; the helper
+    threads then find the views cached). Returns {analyzer: failure metric} of the analyzers whose filter failed:
+    each fails alone, with the exception a Compliance over the same text carries."""
+    wanted = {}
+    for a in analyzers:
+        if getattr(a, "_trailing_where", False) and a.where is not None:
+            cols = a.groupingColumns() if isinstance(a, GroupingAnalyzer) else [a.column]
+            wanted.setdefault(a.where, ([], []))
+            wanted[a.where][0].append(a)
+            wanted[a.where][1].extend(c for c in cols if c in data)
+    failures = {}
+    for where, (group, cols) in wanted.items():
+        try:
+            filters.view(data, where, cols)
+        except Exception as e:
+            for a in group:
+                failures[a] = a.toFailureMetric(e)
+    return failures
+
+
 class AnalysisRunner:
     """R/AnalysisRunner.scala:46-548."""
 
@@ -523,33 +566,45 @@ class AnalysisRunner:
                 wideKll[a] = a.toFailureMetric(e)
         kllAnalyzers = [a for a in kllAnalyzers if a not in wideKll]
         preconditionFailures = preconditionFailures + AnalyzerContext(wideKll)
+        # `where` on grouping analyzers / ApproxQuantile: the run's filtered views, one evaluation per text
+        filters = engine.FilterCache()
+        filterFailures = _prepare_filters(data, passed, filters)
+        if filterFailures:
+            grouping = [a for a in grouping if a not in filterFailures]
+            scanning = [a for a in scanning if a not in filterFailures]
+            preconditionFailures = preconditionFailures + AnalyzerContext(filterFailures)
         by_cols = {}
         for a in grouping:
-            by_cols.setdefault(tuple(sorted(a.groupingColumns())), []).append(a)
+            by_cols.setdefault(_grouping_key(a), []).append(a)
         sets = list(by_cols.items())
 
-        def run_set(cols, group):
-            _, metrics = AnalysisRunner._runGroupingAnalyzers(data, list(cols), group, aggregateWith, saveStatesWith)
+        def run_set(key, group):
+            cols, where = key
+            try:
+                src = data if where is None else filters.view(data, where, list(cols))
+            except Exception as e:
+                return AnalyzerContext({a: a.toFailureMetric(e) for a in group})
+            _, metrics = AnalysisRunner._runGroupingAnalyzers(src, list(cols), group, aggregateWith, saveStatesWith)
             return metrics
-        # the grouping builds (one per grouping-column set) and the scanning / KLL passes read the table independently:
+        # the grouping builds (one per grouping-column set and `where`) and the scanning / KLL passes read the table independently:
         # each set's build runs on its own helper context meanwhile (Spark runs them as separate jobs; at most three
         # helpers, the rest -- or the last set when nothing else runs -- on this thread)
         others = bool(scanning or kllAnalyzers)
         with _Helpers() as helpers:
             here = []
-            for k, (cols, group) in enumerate(sets):
+            for k, (key, group) in enumerate(sets):
                 h = None
                 if k < 3 and (others or k < len(sets) - 1):
-                    h = helpers.beside(lambda cols=cols, group=group: run_set(cols, group), "group%d" % k)
+                    h = helpers.beside(lambda key=key, group=group: run_set(key, group), "group%d" % k)
                 if h is None:
-                    here.append((cols, group))
+                    here.append((key, group))
             kllMetrics = AnalyzerContext.empty()
             if kllAnalyzers:
                 kllMetrics = KLLRunner.computeKLLSketchesInExtraPass(data, kllAnalyzers, aggregateWith, saveStatesWith)
-            nonGrouped = AnalysisRunner._runScanningAnalyzers(data, scanning, aggregateWith, saveStatesWith)
+            nonGrouped = AnalysisRunner._runScanningAnalyzers(data, scanning, aggregateWith, saveStatesWith, filters)
             grouped = AnalyzerContext.empty()
-            for cols, group in here:
-                grouped = grouped + run_set(cols, group)
+            for key, group in here:
+                grouped = grouped + run_set(key, group)
             for h in helpers.pending:
                 grouped = grouped + h.result()
         return preconditionFailures + nonGrouped + grouped + kllMetrics
@@ -580,19 +635,40 @@ class AnalysisRunner:
         grouping = [a for a in analyzers if isinstance(a, GroupingAnalyzer) or
                     (isinstance(a, Histogram) and a.binningUdf is None)]
         whole = AnalyzerContext.empty()
+        # `where` on grouping analyzers / ApproxQuantile over the whole shard: every chunk's key columns under the
+        # chunk's own masked bitmaps (engine.FilterCache), then seen as one table like the unfiltered columns
+        filters = engine.FilterCache()
+        if whole_table:
+            failed = _prepare_filters(data, [a for a in analyzers if Preconditions.findFirstFailing(
+                data.schema, a.preconditions()) is None], filters)
+            if failed:
+                whole = whole + AnalyzerContext(failed)
+                analyzers = [a for a in analyzers if a not in failed]
+                grouping = [a for a in grouping if a not in failed]
+
+        def filtered(view, where, kept):
+            view.filtered_where, view.kept_rows = where, kept
+            return view
         if grouping and whole_table:
             analyzers = [a for a in analyzers if a not in set(grouping)]
             by_set = {}
             for a in grouping:
-                key = ("\x00histogram", a.column) if isinstance(a, Histogram) else tuple(sorted(a.groupingColumns()))
+                key = ("\x00histogram", a.column) if isinstance(a, Histogram) else _grouping_key(a)
                 by_set.setdefault(key, []).append(a)
-            sets = [((k[1],) if k[0] == "\x00histogram" else k, g) for k, g in by_set.items()]
+            sets = [(((k[1],), None) if k[0] == "\x00histogram" else k, g) for k, g in by_set.items()]
             # each grouping-column set on its own helper context (at most three; the rest, or the last set when
             # nothing else runs, on this thread), beside the other analyzers' passes (see doAnalysisRun)
-            for k, (cset, group) in enumerate(sets):
-                def run_set(cset=cset, group=group):
+            for k, ((cset, where), group) in enumerate(sets):
+                def run_set(cset=cset, where=where, group=group):
                     cols = [c for c in cset if c in data]
-                    return AnalysisRunner.doAnalysisRun(data.grouping_view(cols), group, aggregateWith, saveStatesWith)
+                    if where is None:
+                        return AnalysisRunner.doAnalysisRun(data.grouping_view(cols), group, aggregateWith, saveStatesWith)
+                    try:
+                        src = filters.view(data, where, cols)
+                    except Exception as e:
+                        return AnalyzerContext({a: a.toFailureMetric(e) for a in group})
+                    return AnalysisRunner.doAnalysisRun(filtered(src.grouping_view(cols), where, src.kept_rows), group,
+                                                        aggregateWith, saveStatesWith)
                 last_here = not analyzers and k == len(sets) - 1
                 h = None if last_here or k >= 3 else helpers.beside(run_set, "group%d" % k)
                 if h is None:
@@ -606,8 +682,21 @@ class AnalysisRunner:
         # per-partition digests (QuantileSummaries.merge)
         quant = [a for a in analyzers if isinstance(a, (ApproxQuantile, ApproxQuantiles))]
         if quant and whole_table:
-            cols = sorted({a.column for a in quant if a.column in data})
-            whole = whole + AnalysisRunner.doAnalysisRun(data.parted(cols), quant, aggregateWith, saveStatesWith)
+            by_where = {}
+            for a in quant:
+                by_where.setdefault(getattr(a, "where", None), []).append(a)
+            for where, group in by_where.items():
+                cols = sorted({a.column for a in group if a.column in data})
+                if where is None:
+                    src = data.parted(cols)
+                else:
+                    try:
+                        view = filters.view(data, where, cols)
+                    except Exception as e:
+                        whole = whole + AnalyzerContext({a: a.toFailureMetric(e) for a in group})
+                        continue
+                    src = filtered(view.parted(cols), where, view.kept_rows)
+                whole = whole + AnalysisRunner.doAnalysisRun(src, group, aggregateWith, saveStatesWith)
             analyzers = [a for a in analyzers if not isinstance(a, (ApproxQuantile, ApproxQuantiles))]
             if not analyzers:
                 for h in helpers.pending:
@@ -642,7 +731,7 @@ class AnalysisRunner:
         by_cols = {}
         for a in analyzers:
             if isinstance(a, GroupingAnalyzer):
-                by_cols.setdefault(tuple(sorted(a.groupingColumns())), []).append(a)
+                by_cols.setdefault(_grouping_key(a), []).append(a)
         stateless = set()
         for group in by_cols.values():
             if not any(p.load(a) is not None for p in providers for a in group):
@@ -662,14 +751,14 @@ class AnalysisRunner:
         return merged + AnalyzerContext(empty) + AnalyzerContext(failures) + whole
 
     @staticmethod
-    def _runScanningAnalyzers(data, analyzers, aggregateWith=None, saveStatesTo=None):
+    def _runScanningAnalyzers(data, analyzers, aggregateWith=None, saveStatesTo=None, filters=None):
         """R/AnalysisRunner.scala:289-336: one fused dq_scan for all shareable analyzers."""
         shareable = [a for a in analyzers if isinstance(a, ScanShareableAnalyzer)]
         others = [a for a in analyzers if not isinstance(a, ScanShareableAnalyzer)]
         results = {}
         if shareable:
             try:
-                batch = ScanBatch(data)
+                batch = ScanBatch(data, filters)
                 offsets = []
                 for a in shareable:
                     try:
@@ -767,7 +856,7 @@ class AnalysisRunner:
                 res[a] = m
         by_cols = {}
         for a in grouping:
-            by_cols.setdefault(tuple(sorted(a.groupingColumns())), []).append(a)
+            by_cols.setdefault(_grouping_key(a), []).append(a)
         out = pre + AnalyzerContext(res)
         for cols, group in by_cols.items():
             states = [agg.load(a) for a in group if agg.load(a) is not None]

@@ -327,9 +327,26 @@ typedef enum dq_scan_kernel {
     DQ_KERNEL_DICT_COUNTS = 12,   /* dict_counts_kernel: every (dictionary column, where) slot of a call          */
     DQ_KERNEL_DICT_FOLD = 13,     /* dict_fold_kernel: the per-entry fold of a dq_dict_scan call                  */
     DQ_KERNEL_DICT_DECODE = 14,   /* dq_dict_decode calls that copied bytes (a kept column handed on decoded)     */
-    DQ_KERNEL_COUNT = 15
+    DQ_KERNEL_FILTER_VALIDITY = 15, /* filter_validity_kernel: a `where` ANDed into key-column validity bitmaps   */
+    DQ_KERNEL_COUNT = 16
 } dq_scan_kernel;
 int64_t dq_scan_kernel_launches(const dq_ctx* ctx, int32_t kernel);
+
+/* A `where` filter as validity bitmaps, for the analyzers that take no filter argument on the device (the grouping
+ * analyzers, ApproxQuantile): they skip NULL cells -- a grouping drops the rows whose key columns are all NULL -- so a
+ * row the filter drops is a row whose key cells are NULL. `pred` is evaluated over `columns` (host or device columns
+ * of nrows rows, as dq_scan takes them: the same validation, the same kernels, SQL three-valued logic) and, in one
+ * further kernel launch, out_validity_dev[j] = TRUE(pred) & validity(columns[target_columns[j]]) for j in
+ * [0, ntargets), ntargets <= 32; a target without a bitmap counts as all ones. A target need not be read by `pred`,
+ * and only its validity is read (device bitmaps 8-B aligned). Every output is a device buffer, 8-B aligned,
+ * LSB-first, (nrows + 63) / 64 words: EVERY word is written, and bits at and past nrows are 0 whatever the input
+ * bitmaps hold there. *true_rows = the rows on which `pred` is TRUE. nrows == 0 launches nothing.
+ * Status: as dq_scan for the predicate (DQ_ERR_PREDICATE, and DQ_ERR_UNSUPPORTED with dq_scan's texts for a regex past
+ * its backtracking budget or a string only Double.parseDouble's arbitrary-precision path converts; the outputs are
+ * then undefined); DQ_ERR_ALIGNMENT for a misaligned bitmap; DQ_ERR_UNSUPPORTED on a multi-device context. */
+int dq_filter_validity(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, const dq_predicate* pred,
+                       const int32_t* target_columns, int ntargets, uint8_t* const* out_validity_dev,
+                       int64_t* true_rows);
 
 /* ---------------------------------------------------------------------------------------------
  * Dictionary-encoded STRING columns (Arrow dictionary<values=string, indices=int32>, as parquet writes categorical
