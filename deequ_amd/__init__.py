@@ -20,6 +20,7 @@ from .runners import (AnalysisRunner, KLLRunner, AnalysisRunBuilder, AnalyzerCon
                       ScanBatch)
 from .checks import (Check, CheckLevel, CheckStatus, ConstraintStatus, ConstrainableDataTypes, VerificationSuite,
                      VerificationResult)
+from .rowlevel import RowLevelResults
 from .table import ChunkedTable, Table, Column
 from .profiles import (ColumnProfiler, ColumnProfilerRunner, ColumnProfilerRunBuilder, ColumnProfiles,
                        StandardColumnProfile, NumericColumnProfile, DataTypeInstances)

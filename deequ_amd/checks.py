@@ -3,6 +3,8 @@
 M/constraints/AnalysisBasedConstraint.scala), as a thin host layer: a run collects every check's
 required analyzers and hands them to ONE AnalysisRunner.doAnalysisRun (so all scan-shareable
 metrics of all checks come from one fused dq_scan), then evaluates the assertions on the metrics.
+VerificationResult.rowLevelResultsAsTable adds one pass / fail column per check to the data (rowlevel.py: the
+per-row outcomes are computed and kept on the GPU).
 Anomaly detection, KLL sketches, metrics repositories and file output are out of scope.
 """
 import enum
@@ -373,6 +375,17 @@ class VerificationResult:
     @staticmethod
     def successMetricsAsJson(result, forAnalyzers=()):
         return AnalyzerContext.successMetricsAsJson(AnalyzerContext(result.metrics), forAnalyzers)
+
+    @staticmethod
+    def rowLevelResultsAsTable(result, data, filteredRow="true", strict=False):
+        """rowLevelResultsAsDataFrame of later deequ releases: `data` plus one BOOLEAN column per check of `result`
+        that has a row-level constraint, named by the check's description; row i is the AND of those constraints'
+        outcomes on row i. Returns a rowlevel.RowLevelResults (the table, per-check and per-constraint counts, and
+        failedRowsTable / passedRowsTable). `filteredRow`: the outcome of a row a constraint's `where` leaves out,
+        "true" (deequ's FilteredRowOutcome.TRUE) or "null". A constraint that cannot be evaluated per row is listed in
+        `.skipped`, or raises with `strict`."""
+        from .rowlevel import row_level_results
+        return row_level_results(result, data, filteredRow, strict)
 
 
 class VerificationRunBuilder:

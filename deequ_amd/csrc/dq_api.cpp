@@ -1029,6 +1029,205 @@ int dq_filter_validity(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t
     return DQ_OK;
 }
 
+// Every predicate goes through dq_scan's own stages as the `where` of one dummy Size op planned for the bitmap pass, as
+// in dq_filter_validity: run_predicates leaves each TRUE bitmap in the arena, once per predicate however many terms and
+// filters name it, and the scan launch itself is never issued. One row_outcomes_kernel launch (rowlevel.hip) then folds
+// the terms into every check's outputs and the counts. A predicate `column <op> constant` over a numeric column -- the
+// form dq_scan fuses into a value scan -- gets no pass of its own: that launch evaluates it from the column
+// (RowInlineDev, up to kRowInline per call), so the call costs no more predicate launches than the same predicates do as
+// one scan's Compliance ops.
+int dq_row_outcomes(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, const dq_predicate* preds, int npreds,
+                    const dq_row_term* terms, int nterms, const dq_row_check* checks, int nchecks, uint32_t flags,
+                    int64_t* term_counts, int64_t* check_counts) {
+    if (!ctx) return DQ_ERR_INVALID_ARGUMENT;
+    ctx->err.clear();
+    if (ncols < 0 || nrows < 0 || npreds < 0 || nterms < 0 || nchecks <= 0 || !checks || !check_counts ||
+        (ncols > 0 && !columns) || (npreds > 0 && !preds) || (nterms > 0 && (!terms || !term_counts)))
+        return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: invalid arguments");
+    if (!ctx->subs.empty()) return fail(ctx, DQ_ERR_UNSUPPORTED, "dq_row_outcomes: multi-device contexts are not supported");
+    if (nterms > DQ_ROW_MAX_TERMS || nchecks > DQ_ROW_MAX_CHECKS)
+        return fail(ctx, DQ_ERR_UNSUPPORTED, "dq_row_outcomes: %d terms over %d checks, at most %d terms and %d checks per call",
+                    nterms, nchecks, DQ_ROW_MAX_TERMS, DQ_ROW_MAX_CHECKS);
+    const bool null_mode = (flags & DQ_ROW_FILTERED_NULL) != 0;
+    for (int t = 0; t < nterms; ++t) {
+        const dq_row_term& tm = terms[t];
+        if (tm.check < 0 || tm.check >= nchecks)
+            return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: term %d names check %d", t, tm.check);
+        if (tm.kind == DQ_ROW_BITS) {
+            if (!tm.pass_bits || !tm.considered_bits)
+                return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: term %d has no bitmaps", t);
+            if (((uintptr_t)tm.pass_bits | (uintptr_t)tm.considered_bits) & 7)
+                return fail(ctx, DQ_ERR_ALIGNMENT, "dq_row_outcomes: bitmaps must be 8-B aligned (term %d)", t);
+            continue;
+        }
+        if (tm.where < -1 || tm.where >= npreds)
+            return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: term %d names predicate %d as its where", t, tm.where);
+        if (tm.kind == DQ_ROW_PREDICATE) {
+            if (tm.index < 0 || tm.index >= npreds)
+                return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: term %d names predicate %d", t, tm.index);
+        } else if (tm.kind == DQ_ROW_NOT_NULL) {
+            if (tm.index < 0 || tm.index >= ncols)
+                return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: term %d names column %d", t, tm.index);
+            const dq_column& col = columns[tm.index];
+            if (col.length != nrows)
+                return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "column %d has %lld rows, batch has %lld", tm.index, (long long)col.length,
+                            (long long)nrows);
+            if ((col.flags & DQ_COL_DEVICE) && ((uintptr_t)col.validity & 7))
+                return fail(ctx, DQ_ERR_ALIGNMENT, "dq_row_outcomes: bitmaps must be 8-B aligned (column %d)", tm.index);
+        } else {
+            return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: term %d has kind %d", t, tm.kind);
+        }
+    }
+    for (int c = 0; c < nchecks; ++c) {
+        const dq_row_check& ck = checks[c];
+        if (!ck.pass_bits || !ck.values || (null_mode && !ck.validity))
+            return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: check %d lacks an output buffer", c);
+        if (((uintptr_t)ck.pass_bits & 7) || ((uintptr_t)ck.values & 15) || (null_mode && ((uintptr_t)ck.validity & 7)))
+            return fail(ctx, DQ_ERR_ALIGNMENT, "dq_row_outcomes: check %d: bitmaps must be 8-B, the byte column 16-B aligned", c);
+    }
+    for (int t = 0; t < 2 * nterms; ++t) term_counts[t] = 0;
+    for (int c = 0; c < 2 * nchecks; ++c) check_counts[c] = 0;
+    DQ_HIP(ctx, hipSetDevice(ctx->device));
+
+    std::vector<dq_op> ops((size_t)std::max(npreds, 1));
+    for (int p = 0; p < npreds; ++p) ops[p] = dq_op{DQ_OP_SIZE, {-1, -1}, p, -1};
+    ScanCall sc{ctx, columns, ncols, nrows, ops.data(), npreds, preds, npreds};
+    std::string msg;
+    int rc;
+    if (npreds > 0) {
+        rc = validate_scan(columns, ncols, nrows, ops.data(), npreds, preds, npreds, &sc.use, &msg);
+        if (rc) return fail(ctx, rc, "%s", msg.c_str());
+    } else {
+        sc.use.col_used.assign((size_t)std::max(ncols, 1), 0);
+    }
+    if (nrows == 0) return DQ_OK;
+    Stager up{ctx};
+    std::vector<int> inline_of((size_t)std::max(npreds, 1), -1);  // predicate -> inline predicate of the launch
+    PredTerm inline_term[kRowInline];
+    int ninline = 0;
+    if (npreds > 0) {
+        sc.options.where_masks = false;  // the bitmap pass: TRUE / NOT-NULL bitmaps from a predicate launch
+        sc.options.pred_vm = pred_vm_forced();
+        rc = plan_scan(columns, ncols, nrows, ops.data(), npreds, preds, npreds, sc.use, sc.options, &sc.plan, &msg);
+        if (rc) return fail(ctx, rc, "%s", msg.c_str());
+        // `column <op> constant` predicates are evaluated by the row_outcomes launch itself: no pass, no bitmaps
+        for (int p = 0; p < npreds && ninline < kRowInline && !sc.options.pred_vm; ++p) {
+            PredSimple ps;
+            if (!compile_simple_predicate(preds[p], columns, ncols, ps) || ps.nterms != 1 || ps.nb != 1 || ps.b[0] != 0 ||
+                ps.t[0].op < DQ_P_EQ || ps.t[0].op > DQ_P_GE)
+                continue;
+            inline_of[p] = ninline;
+            inline_term[ninline++] = ps.t[0];
+            sc.plan.pred_pass[p] = 0;
+        }
+        if ((rc = scan_geometry(sc))) return rc;
+        sc.L = layout_scan(sc.plan, sc.geo, sc.use, columns, ncols, nrows, npreds, preds, npreds, true);
+        if ((rc = ensure_arena(ctx, sc.L.arena_bytes))) return rc;
+    }
+    const size_t count_bytes = sizeof(unsigned long long) * kRowCounters;
+    if ((rc = ensure_pinned(ctx, (npreds > 0 ? sc.L.pinned_bytes : 0) + count_bytes + 64))) return rc;  // + the counts' read-back
+    if (npreds > 0 && (rc = stage_columns(sc))) return rc;
+    DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the pinned buffer may still be read by a previous call's copies
+    if (npreds > 0 && (rc = run_predicates(sc, up))) return rc;
+
+    // terms sorted by check; a NOT_NULL host column no predicate reads: only its bitmap goes to the device
+    std::vector<int> order((size_t)nterms);
+    for (int t = 0; t < nterms; ++t) order[t] = t;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return terms[a].check < terms[b].check; });
+    ScratchBuffers buf(ctx);
+    const size_t bitmap_bytes = (size_t)(nrows + 7) / 8;
+    std::vector<const uint8_t*> staged((size_t)std::max(ncols, 1), nullptr);
+    RowOutcomeArgs args;
+    memset(&args, 0, sizeof(args));
+    args.nterms = nterms;
+    args.nchecks = nchecks;
+    args.null_mode = null_mode ? 1 : 0;
+    args.ninline = ninline;
+    for (int k = 0; k < ninline; ++k) {  // the column is one a predicate reads: staged, or read in place
+        const PredTerm& q = inline_term[k];
+        RowInlineDev& d = args.inl[k];
+        d.values = sc.val[q.col];
+        d.validity = (const uint8_t*)sc.valid[q.col];
+        d.spark_type = columns[q.col].spark_type;
+        d.op = q.op;
+        d.dbl = q.dbl;
+        d.ci = q.ci;
+        d.cd = q.cd;
+    }
+    for (int c = 0; c < nchecks; ++c) {
+        args.check[c].pass = (uint64_t*)checks[c].pass_bits;
+        args.check[c].values = checks[c].values;
+        args.check[c].validity = null_mode ? (uint64_t*)checks[c].validity : nullptr;
+    }
+    for (int i = 0, c = 0; c < nchecks; ++c) {
+        args.check[c].term_begin = i;
+        while (i < nterms && terms[order[i]].check == c) ++i;
+        args.check[c].term_end = i;
+    }
+    for (int i = 0; i < nterms; ++i) {
+        const dq_row_term& tm = terms[order[i]];
+        RowTermDev& td = args.term[i];
+        td.src_inline = td.w_inline = -1;
+        if (tm.kind == DQ_ROW_BITS) {
+            td.src = tm.pass_bits;
+            td.src_kind = RS_WORDS;
+            td.w = (const uint64_t*)tm.considered_bits;
+            continue;
+        }
+        if (tm.where >= 0 && inline_of[tm.where] >= 0) td.w_inline = (int16_t)inline_of[tm.where];
+        else td.w = sc.pred_t(tm.where);
+        if (tm.kind == DQ_ROW_PREDICATE) {
+            if (inline_of[tm.index] >= 0) {
+                td.src_kind = RS_INLINE;
+                td.src_inline = (int16_t)inline_of[tm.index];
+            } else {
+                td.src = sc.pred_t(tm.index);
+                td.src_kind = RS_WORDS;
+            }
+            continue;
+        }
+        const int c = tm.index;
+        const dq_column& col = columns[c];
+        const uint8_t* v = nullptr;
+        if (col.flags & DQ_COL_DEVICE) {
+            v = col.validity;
+        } else if (sc.use.col_used[c]) {
+            v = (const uint8_t*)sc.valid[c];
+        } else if (col.validity) {
+            if (!staged[c]) {
+                void* vd = nullptr;
+                DQ_HIP(ctx, buf.alloc(&vd, align_up(bitmap_bytes, 8) + 8));
+                DQ_HIP(ctx, hipMemcpyAsync(vd, col.validity, bitmap_bytes, hipMemcpyHostToDevice, ctx->stream));
+                staged[c] = (const uint8_t*)vd;
+            }
+            v = staged[c];
+        }
+        td.src = v;
+        td.src_kind = v ? RS_VALID_BYTES : RS_ONES;
+    }
+    unsigned long long* dcounts = nullptr;
+    DQ_HIP(ctx, buf.alloc((void**)&dcounts, count_bytes));
+    DQ_HIP(ctx, hipMemsetAsync(dcounts, 0, count_bytes, ctx->stream));
+    if (launch_row_outcomes(args, nrows, dcounts, ctx->stream) != 0)
+        return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: nothing to launch");
+    DQ_HIP(ctx, hipGetLastError());
+    ctx->kernel_launches[DQ_KERNEL_ROW_OUTCOMES]++;
+    if (npreds > 0 && (rc = check_pred_status(sc, up))) {
+        (void)hipStreamSynchronize(ctx->stream);  // staged host bitmaps must outlive the kernels
+        return rc;
+    }
+    void* h = nullptr;
+    if ((rc = up.download(&h, dcounts, count_bytes))) return rc;
+    DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const unsigned long long* hc = (const unsigned long long*)h;
+    for (int i = 0; i < nterms; ++i) {
+        term_counts[2 * order[i]] = (int64_t)hc[2 * i];
+        term_counts[2 * order[i] + 1] = (int64_t)hc[2 * i + 1];
+    }
+    for (int c = 0; c < 2 * nchecks; ++c) check_counts[c] = (int64_t)hc[2 * DQ_ROW_MAX_TERMS + c];
+    return DQ_OK;
+}
+
 // Host columns streamed through HBM in row chunks (tables larger than HBM, or host-resident batches): the copy
 // of chunk i + 1 (its own stream, double-buffered device chunks) overlaps the fused scan of chunk i; every chunk's
 // states land in device memory and the chunks are folded in row order with the reference merges (the partition

@@ -195,6 +195,16 @@ __device__ __forceinline__ fx128 fx_shfl_down(fx128 v, int off) {
     const unsigned long long l2 = __shfl_down(lo, off, 64), h2 = __shfl_down(hi, off, 64);
     return (fx128)(((unsigned __int128)h2 << 64) | l2);
 }
+
+// A validity word of a bitmap that holds exactly vbytes = ceil(nrows / 8) readable bytes: the last word may be short
+// (filter_validity_kernel, row_outcomes_kernel).
+__device__ inline unsigned long long filter_valid_word(const uint8_t* __restrict__ valid, int64_t w, int64_t vbytes) {
+    const int64_t b0 = w * 8;
+    if (b0 + 8 <= vbytes) return *(const unsigned long long*)(valid + b0);
+    unsigned long long v = 0;
+    for (int64_t b = b0; b < vbytes; ++b) v |= (unsigned long long)valid[b] << (8 * (b - b0));
+    return v;
+}
 #endif
 
 }  // namespace dq

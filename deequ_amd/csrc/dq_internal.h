@@ -270,6 +270,52 @@ struct FilterTargets {
     uint64_t* out[kFilterTargets];         // out: TRUE & valid, (nrows + 63) / 64 words
 };
 
+// dq_row_outcomes: the terms and checks of one row_outcomes_kernel launch (rowlevel.hip), passed by value. The terms
+// are sorted by check, so a check's terms are term[term_begin .. term_end).
+enum RowSrcKind : int32_t {
+    RS_ONES = 0,         // no bitmap: every row holds (a column without validity)
+    RS_WORDS = 1,        // whole 64-bit words: a predicate's TRUE bitmap in the arena, a BITS term's pass bitmap
+    RS_VALID_BYTES = 2,  // a column's validity: exactly ceil(nrows / 8) readable bytes, 8-B aligned
+    RS_INLINE = 3,       // the TRUE word of inline predicate src_inline, evaluated by the kernel itself
+};
+// A predicate `column <op> constant` over a fixed-width numeric column (a PredSimple of one comparison, the form dq_scan
+// fuses into a value scan): the kernel evaluates it from the column as pred_simple_kernel would, so it costs no
+// predicate launch and no bitmap round trip through HBM. At most kRowInline per call; the rest take a predicate launch.
+constexpr int kRowInline = 16;
+struct RowInlineDev {
+    const void* values;
+    const uint8_t* validity;  // nullptr = all valid; ceil(nrows / 8) readable bytes
+    int32_t spark_type;
+    int32_t op;   // DQ_P_EQ..DQ_P_GE
+    int32_t dbl;  // compare as double (Spark NaN ordering) instead of as long
+    int32_t pad;
+    int64_t ci;
+    double cd;
+};
+struct RowTermDev {
+    const void* src;    // what must hold for the term to pass (RowSrcKind)
+    const uint64_t* w;  // rows the term considers: whole words (`where` TRUE, or a BITS term's bitmap); nullptr = all
+    int32_t src_kind;
+    int16_t src_inline;  // RS_INLINE: the inline predicate
+    int16_t w_inline;    // >= 0: the `where` is this inline predicate (w is nullptr)
+};
+struct RowCheckDev {
+    uint64_t* pass;      // out: outcome TRUE, (nrows + 63) / 64 words
+    uint8_t* values;     // out: one byte per row, nrows rounded up to 16 bytes
+    uint64_t* validity;  // out (null mode): outcome not NULL
+    int32_t term_begin, term_end;
+};
+struct RowOutcomeArgs {
+    int32_t nterms, nchecks;
+    int32_t null_mode;  // DQ_ROW_FILTERED_NULL
+    int32_t ninline;
+    RowTermDev term[DQ_ROW_MAX_TERMS];
+    RowCheckDev check[DQ_ROW_MAX_CHECKS];
+    RowInlineDev inl[kRowInline];
+};
+// Counters of one launch: (matched, considered) per term, then (TRUE, NULL) rows per check.
+constexpr int kRowCounters = 2 * DQ_ROW_MAX_TERMS + 2 * DQ_ROW_MAX_CHECKS;
+
 inline int elem_of(int32_t spark_type) {
     switch (spark_type) {
         case DQ_TYPE_BOOLEAN: return ET_U8;
@@ -486,6 +532,10 @@ void launch_regex(const PredColumn& col, const int32_t* image_dev, int64_t nrows
 // TRUE rows. Returns non-zero when nrows is 0 or needs more than 2^31 - 1 workgroups.
 int launch_filter_validity(const uint64_t* true_bits, const FilterTargets& targets, int64_t nrows,
                            unsigned long long* true_rows, hipStream_t s);
+// Every check's pass bitmap, byte column and (null mode) validity bitmap, and counts[kRowCounters] (device, zeroed):
+// counts[2 t] / [2 t + 1] += term t's matched / considered rows, counts[2 DQ_ROW_MAX_TERMS + 2 c] / [.. + 1] += check c's
+// TRUE / NULL rows. Returns non-zero when nrows is 0.
+int launch_row_outcomes(const RowOutcomeArgs& args, int64_t nrows, unsigned long long* counts, hipStream_t s);
 void launch_synth_column(int kind, uint64_t seed, int64_t row0, int64_t nrows, void* out, hipStream_t s);
 void launch_synth_freq_keys(int64_t total, int64_t distinct, int64_t row0, int64_t nrows, int64_t* out, hipStream_t s);
 void launch_synth_string_lengths(int kind, uint64_t seed, int64_t row0, int64_t nrows, int32_t* lens, hipStream_t s);

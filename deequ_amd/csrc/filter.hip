@@ -18,15 +18,6 @@ namespace dq {
 constexpr int kFilterBlock = 256;
 constexpr int kFilterWaves = kFilterBlock / 64;
 
-// A validity word of a bitmap that holds exactly vbytes = ceil(nrows / 8) readable bytes: the last word may be short.
-__device__ inline unsigned long long filter_valid_word(const uint8_t* __restrict__ valid, int64_t w, int64_t vbytes) {
-    const int64_t b0 = w * 8;
-    if (b0 + 8 <= vbytes) return *(const unsigned long long*)(valid + b0);
-    unsigned long long v = 0;
-    for (int64_t b = b0; b < vbytes; ++b) v |= (unsigned long long)valid[b] << (8 * (b - b0));
-    return v;
-}
-
 __global__ void __launch_bounds__(kFilterBlock)
 filter_validity_kernel(const uint64_t* __restrict__ true_bits, const FilterTargets T, int64_t nrows, int64_t nwords,
                        unsigned long long* __restrict__ true_rows) {

@@ -2064,6 +2064,23 @@ row_counts_kernel(LookupTable T, int64_t nrows, long long* __restrict__ out) {
         out[r] = (long long)lookup_count(T, r);
 }
 
+// The same join as two bits per row: a wave takes the 64 rows of one bitmap word, and the two ballots of its lanes'
+// counts are the words (count == 1: the row is unique; count > 0: it takes part). Lanes past nrows vote 0, so the
+// tail bits are clear; one lane stores each word.
+__global__ void __launch_bounds__(kFreqBlock)
+row_bits_kernel(LookupTable T, int64_t nrows, int64_t nwords, unsigned long long* __restrict__ unique,
+                unsigned long long* __restrict__ part) {
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * (kFreqBlock / 64);
+    for (int64_t w = (int64_t)blockIdx.x * (kFreqBlock / 64) + (threadIdx.x >> 6); w < nwords; w += stride) {
+        const int64_t r = w * 64 + lane;
+        const unsigned long long c = r < nrows ? lookup_count(T, r) : 0ull;
+        const unsigned long long u = __ballot(c == 1ull), p = __ballot(c > 0ull);
+        if (lane == 0) unique[w] = u;
+        if (lane == 1) part[w] = p;
+    }
+}
+
 }  // namespace
 
 struct dq_ctx;  // defined in dq_api.cpp; only its device/stream are needed here
@@ -3978,6 +3995,31 @@ int dq_freq_row_counts(dq_ctx* ctx, const dq_freq_table* t, int64_t* counts, int
     hipLaunchKernelGGL(row_counts_kernel, dim3(scan_grid((uint64_t)nrows)), dim3(kFreqBlock), 0, s, T, nrows, d);
     DQ_CTX_HIP(ctx, hipGetLastError());
     if (!dev_out) DQ_CTX_HIP(ctx, hipMemcpyAsync(counts, d, (size_t)nrows * 8, hipMemcpyDeviceToHost, s));
+    DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
+    return DQ_OK;
+}
+
+int dq_freq_row_bits(dq_ctx* ctx, const dq_freq_table* t, uint8_t* unique_bits_dev, uint8_t* part_bits_dev, int64_t nrows) {
+    if (!ctx || !t || nrows < 0 || (nrows > 0 && (!unique_bits_dev || !part_bits_dev)))
+        return dq::ctx_fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_freq_row_bits: invalid arguments");
+    if (!t->parts.empty() || t->src_rows < 0 || !t->slots)
+        return dq::ctx_fail(ctx, DQ_ERR_UNSUPPORTED, "dq_freq_row_bits: needs a single-device table built over rows");
+    if (nrows != t->src_rows)
+        return dq::ctx_fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_freq_row_bits: nrows differs from the table's source rows");
+    if (((uintptr_t)unique_bits_dev | (uintptr_t)part_bits_dev) & 7)
+        return dq::ctx_fail(ctx, DQ_ERR_ALIGNMENT, "dq_freq_row_bits: bitmaps must be 8-B aligned");
+    if (nrows == 0) return DQ_OK;
+    DQ_CTX_HIP(ctx, hipSetDevice(t->device));
+    hipStream_t s = dq::ctx_stream(ctx);
+    LookupTable T;
+    T.slots = t->slots;
+    T.ks = t->ks;
+    T.sentinel = t->host_ctr.sentinel;
+    T.bits = t->bits;
+    const int64_t nwords = (nrows + 63) >> 6;
+    hipLaunchKernelGGL(row_bits_kernel, dim3(scan_grid((uint64_t)nrows)), dim3(kFreqBlock), 0, s, T, nrows, nwords,
+                       (unsigned long long*)unique_bits_dev, (unsigned long long*)part_bits_dev);
+    DQ_CTX_HIP(ctx, hipGetLastError());
     DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
     return DQ_OK;
 }

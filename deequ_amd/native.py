@@ -62,7 +62,7 @@ FREQ_PATHS = ("fast", "fast_narrow", "fast_done", "exact", "partitioned", "sorte
               "split_buckets", "long_tuples")
 SCAN_KERNELS = ("striped", "striped_heavy", "heavy8", "heavy8_full", "bits", "pred_simple", "pred_vm", "regex",
                 "strings", "where_fused", "where_masks", "decimal128", "dict_counts", "dict_fold", "dict_decode",
-                "filter_validity")
+                "filter_validity", "row_outcomes")
 
 # Every symbol include/dq.h declares (checked by tests/test_native_abi.py).
 EXPORTED_SYMBOLS = (
@@ -76,7 +76,7 @@ EXPORTED_SYMBOLS = (
     "dq_kll_merge_states", "dq_scratch_trim", "dq_frequencies_parts", "dq_set_priority",
     "dq_schema_validate", "dq_schema_launch_count", "dq_gather_rows", "dq_parse_int32", "dq_parse_decimal",
     "dq_parse_timestamp", "dq_split_rows", "dq_split_row_is_test", "dq_dec128_to_double",
-    "dq_dict_scan", "dq_dict_counts", "dq_dict_decode", "dq_filter_validity",
+    "dq_dict_scan", "dq_dict_counts", "dq_dict_decode", "dq_filter_validity", "dq_freq_row_bits", "dq_row_outcomes",
 )
 
 
@@ -90,6 +90,20 @@ class DqDictColumn(ctypes.Structure):
     """dq_dict_column: a dictionary-encoded STRING column (device buffers)."""
     _fields_ = [("flags", ctypes.c_uint32), ("pad", ctypes.c_uint32), ("length", ctypes.c_int64),
                 ("indices", ctypes.c_void_p), ("validity", ctypes.c_void_p), ("dictionary", DqColumn)]
+
+
+ROW_NOT_NULL, ROW_PREDICATE, ROW_BITS = 1, 2, 3  # dq_row_term_kind
+ROW_FILTERED_NULL = 0x1
+ROW_MAX_TERMS, ROW_MAX_CHECKS = 64, 16
+
+
+class DqRowTerm(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("index", ctypes.c_int32), ("where", ctypes.c_int32), ("check", ctypes.c_int32),
+                ("pass_bits", ctypes.c_void_p), ("considered_bits", ctypes.c_void_p)]
+
+
+class DqRowCheck(ctypes.Structure):
+    _fields_ = [("pass_bits", ctypes.c_void_p), ("values", ctypes.c_void_p), ("validity", ctypes.c_void_p)]
 
 
 class DqConst(ctypes.Structure):
@@ -336,6 +350,9 @@ def load_library(path=None):
             "dq_dict_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
             "dq_filter_validity": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p,
                                            c_void_p]),
+            "dq_freq_row_bits": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64]),
+            "dq_row_outcomes": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                        c_int, c_uint32, c_void_p, c_void_p]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name)
@@ -688,6 +705,29 @@ class Context:
                                                tgt.ctypes.data, len(tgt), outs, ctypes.byref(true_rows)),
                    "dq_filter_validity")
         return int(true_rows.value)
+
+    def freq_row_bits(self, table_handle, unique_ptr, part_ptr, nrows):
+        """dq_freq_row_bits: per source row of a frequency table, `group count == 1` and `group count > 0` as two
+        device bitmaps ((nrows + 63) // 64 words each)."""
+        self._after_torch_stream()
+        self.check(self.lib.dq_freq_row_bits(self.handle, table_handle, ctypes.c_void_p(unique_ptr),
+                                             ctypes.c_void_p(part_ptr), int(nrows)), "dq_freq_row_bits")
+
+    def row_outcomes(self, columns, nrows, preds, terms, checks, flags=0):
+        """dq_row_outcomes: `terms` (DqRowTerm) over `columns` / `preds` (DqPredicate) folded into the output buffers of
+        `checks` (DqRowCheck) in one launch; returns ([(matched, considered)] per term, [(TRUE rows, NULL rows)] per
+        check)."""
+        self._after_torch_stream()
+        col_arr = (DqColumn * max(len(columns), 1))(*columns)
+        pred_arr = (DqPredicate * max(len(preds), 1))(*preds)
+        term_arr = (DqRowTerm * max(len(terms), 1))(*terms)
+        check_arr = (DqRowCheck * max(len(checks), 1))(*checks)
+        tc = (ctypes.c_int64 * (2 * max(len(terms), 1)))()
+        cc = (ctypes.c_int64 * (2 * max(len(checks), 1)))()
+        self.check(self.lib.dq_row_outcomes(self.handle, col_arr, len(columns), int(nrows), pred_arr, len(preds), term_arr,
+                                            len(terms), check_arr, len(checks), int(flags), tc, cc), "dq_row_outcomes")
+        return ([(int(tc[2 * i]), int(tc[2 * i + 1])) for i in range(len(terms))],
+                [(int(cc[2 * i]), int(cc[2 * i + 1])) for i in range(len(checks))])
 
     def split_rows(self, nrows, row0, seed, test_ratio, train_ptr, test_ptr):
         """dq_split_rows into two device bitmaps (either pointer may be None); returns (num_train, num_test)."""

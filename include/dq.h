@@ -328,7 +328,8 @@ typedef enum dq_scan_kernel {
     DQ_KERNEL_DICT_FOLD = 13,     /* dict_fold_kernel: the per-entry fold of a dq_dict_scan call                  */
     DQ_KERNEL_DICT_DECODE = 14,   /* dq_dict_decode calls that copied bytes (a kept column handed on decoded)     */
     DQ_KERNEL_FILTER_VALIDITY = 15, /* filter_validity_kernel: a `where` ANDed into key-column validity bitmaps   */
-    DQ_KERNEL_COUNT = 16
+    DQ_KERNEL_ROW_OUTCOMES = 16,  /* row_outcomes_kernel: the per-check row outcomes of one dq_row_outcomes call  */
+    DQ_KERNEL_COUNT = 17
 } dq_scan_kernel;
 int64_t dq_scan_kernel_launches(const dq_ctx* ctx, int32_t kernel);
 
@@ -347,6 +348,60 @@ int64_t dq_scan_kernel_launches(const dq_ctx* ctx, int32_t kernel);
 int dq_filter_validity(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, const dq_predicate* pred,
                        const int32_t* target_columns, int ntargets, uint8_t* const* out_validity_dev,
                        int64_t* true_rows);
+
+/* ---------------------------------------------------------------------------------------------
+ * Row-level results (VerificationResult.rowLevelResultsAsDataFrame of later deequ releases): one
+ * BOOLEAN outcome column per check, the AND of its terms, written by ONE kernel launch next to the table in HBM.
+ * ------------------------------------------------------------------------------------------- */
+typedef enum dq_row_term_kind {
+    DQ_ROW_NOT_NULL = 1,   /* Completeness: passes where columns[index] is not NULL                              */
+    DQ_ROW_PREDICATE = 2,  /* Compliance / PatternMatch: passes where preds[index] is TRUE (FALSE and NULL fail) */
+    DQ_ROW_BITS = 3        /* caller-supplied device bitmaps, as dq_freq_row_bits writes them (uniqueness)       */
+} dq_row_term_kind;
+
+typedef struct dq_row_term {
+    int32_t kind;                    /* dq_row_term_kind                                                         */
+    int32_t index;                   /* NOT_NULL: column index; PREDICATE: predicate index; BITS: not read       */
+    int32_t where;                   /* predicate index of the term's `where`, -1 = none; BITS: not read         */
+    int32_t check;                   /* index of the check the term belongs to                                   */
+    const uint8_t* pass_bits;        /* BITS: rows that pass; device, 8-B aligned, (nrows + 63) / 64 words       */
+    const uint8_t* considered_bits;  /* BITS: rows the term considers; the same shape                            */
+} dq_row_term;
+
+typedef struct dq_row_check {
+    uint8_t* pass_bits;  /* out: rows whose outcome is TRUE; device, 8-B aligned, (nrows + 63) / 64 words            */
+    uint8_t* values;     /* out: the BOOLEAN column, one byte per row; device, 16-B aligned, nrows rounded up to 16 B */
+    uint8_t* validity;   /* out, DQ_ROW_FILTERED_NULL only: rows whose outcome is not NULL; shaped as pass_bits      */
+} dq_row_check;
+
+#define DQ_ROW_FILTERED_NULL 0x1u /* a row a term does not consider is NULL (default: it passes) */
+#define DQ_ROW_MAX_TERMS 64
+#define DQ_ROW_MAX_CHECKS 16
+
+/* The outcome of every row under every check. Term t considers the rows on which its `where` is TRUE (every row
+ * without one; a BITS term the rows of considered_bits) and passes the considered rows on which its source holds.
+ * term_counts[2 t] = rows considered and passed (`matched`), term_counts[2 t + 1] = rows considered: for NOT_NULL and
+ * PREDICATE terms exactly the NumMatchesAndCount that dq_scan returns for Completeness / Compliance under the same
+ * `where`. A check's outcome on a row is the AND of its terms (no terms: TRUE):
+ *   default               a term a row is not considered by passes it. TRUE unless a term fails; no validity bitmap.
+ *   DQ_ROW_FILTERED_NULL  such a term is NULL there; SQL three-valued AND: FALSE if any term fails, else NULL if any
+ *                         term is NULL, else TRUE. checks[c].validity is written.
+ * check_counts[2 c] = TRUE rows, check_counts[2 c + 1] = NULL rows (0 without the flag); the FALSE rows are the rest.
+ * `columns` / `preds` are host or device columns of nrows rows and predicates as dq_scan takes them (the same
+ * validation, SQL three-valued logic, the same predicate kernels -- but `column <op> constant` over a numeric column,
+ * which dq_scan fuses into a value scan, is evaluated by the row_outcomes launch itself, so the call issues no more
+ * predicate launches than a scan); every predicate of `preds` is evaluated exactly once, whatever
+ * the number of terms and filters that name it, and only the validity of a NOT_NULL column is read (device bitmaps 8-B
+ * aligned). Outputs: EVERY word of pass_bits / validity is written, bits at and past nrows are 0 whatever the inputs
+ * hold there; values[i] is 0 / 1 for i < nrows (0 where the outcome is FALSE or NULL) and 0 from nrows up to the next
+ * multiple of 16. term_counts (2 * nterms) and check_counts (2 * nchecks) are host memory. nrows == 0 launches nothing.
+ * Status: as dq_scan for the predicates (the outputs are then undefined); DQ_ERR_UNSUPPORTED for more than
+ * DQ_ROW_MAX_TERMS terms or DQ_ROW_MAX_CHECKS checks (the caller splits by check) and on a multi-device context;
+ * DQ_ERR_ALIGNMENT for a misaligned bitmap or a values buffer not 16-B aligned; DQ_ERR_INVALID_ARGUMENT for an index out
+ * of range, a missing buffer, or a NOT_NULL column whose length is not nrows. */
+int dq_row_outcomes(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, const dq_predicate* preds, int npreds,
+                    const dq_row_term* terms, int nterms, const dq_row_check* checks, int nchecks, uint32_t flags,
+                    int64_t* term_counts, int64_t* check_counts);
 
 /* ---------------------------------------------------------------------------------------------
  * Dictionary-encoded STRING columns (Arrow dictionary<values=string, indices=int32>, as parquet writes categorical
@@ -502,6 +557,16 @@ int dq_freq_mutual_information(dq_ctx* ctx, const dq_freq_table* joint, const dq
  * tables (A/MutualInformation.scala:50-74); the sharded MutualInformation attaches px / py to exchanged groups
  * with it. `counts` holds nrows entries (a device pointer with DQ_FREQ_PAIRS_DEVICE). */
 int dq_freq_row_counts(dq_ctx* ctx, const dq_freq_table* table, int64_t* counts, int64_t nrows, uint32_t flags);
+
+/* The same join as two bits per row instead of an 8-byte count: bit i of unique_bits_dev = row i's group has count 1
+ * (the row is unique under the table's keys), bit i of part_bits_dev = its group has a count > 0 (the row takes part:
+ * some key column is not NULL). Both are device buffers, 8-B aligned, LSB-first, (nrows + 63) / 64 words; EVERY word is
+ * written, and bits at and past nrows are 0. One wave takes 64 consecutive rows and stores the two ballot words; the
+ * outputs are the pass / considered bitmaps of a DQ_ROW_BITS term. The table and nrows as dq_freq_row_counts takes them,
+ * with its errors (a single-device table built over rows that still has its slot table: DQ_ERR_UNSUPPORTED otherwise;
+ * nrows must be the table's source rows); DQ_ERR_ALIGNMENT for a misaligned bitmap. nrows == 0 launches nothing. */
+int dq_freq_row_bits(dq_ctx* ctx, const dq_freq_table* table, uint8_t* unique_bits_dev, uint8_t* part_bits_dev,
+                     int64_t nrows);
 
 /* ApproxQuantile / ApproxQuantiles (A/ApproxQuantile.scala:28-103, A/ApproxQuantiles.scala:39-101): replaces the
  * per-row PercentileDigest.add of StatefulApproxQuantile.update (C/StatefulApproxQuantile.scala:65-72). Computes
