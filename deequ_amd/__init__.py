@@ -31,6 +31,9 @@ from .suggestions import (ConstraintSuggestionRunner, ConstraintSuggestionRunBui
                           RetainCompletenessRule, RetainTypeRule, CategoricalRangeRule,
                           FractionalCategoricalRangeRule, NonNegativeNumbersRule, UniqueIfApproximatelyUniqueRule,
                           split_train_test)
+from .comparison import (ComparisonResult, ComparisonSucceeded, ComparisonFailed, ReferentialIntegrity,
+                         DataSynchronization, DatasetMatchState, DatasetMatchAnalyzer)
+from . import comparison
 from . import distributed
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -177,6 +177,13 @@ class Check:
             return _named(u, assertion, "UniquenessConstraint(%r)" % u, hint=hint)
         return self._filterable(mk)
 
+    def doesDatasetMatch(self, otherDataset, keyColumnMappings, assertion, matchColumnMappings=None, hint=None):
+        """Check.doesDatasetMatch of the later deequ releases: the share of rows that match
+        `otherDataset` on the key mappings (and the match mappings) meets `assertion`."""
+        from .comparison import DatasetMatchAnalyzer
+        a = DatasetMatchAnalyzer(otherDataset, keyColumnMappings, assertion, matchColumnMappings)
+        return self.addConstraint(_named(a, assertion, "DatasetMatchConstraint(%r)" % a, hint=hint))
+
     def hasDistinctness(self, columns, assertion, hint=None):
         def mk(where):
             d = A.Distinctness(list(columns), where)

@@ -2081,6 +2081,111 @@ row_bits_kernel(LookupTable T, int64_t nrows, int64_t nwords, unsigned long long
     }
 }
 
+// ---- semi-join probe: the rows of another table against a built table (dq_freq_probe) ------------------------------
+// SQL '=' between the probe row and a key of the table: a NULL component on either side never matches (row_key and
+// rows_equal are null-safe, the grouping's equality, so neither serves here).
+
+// Fingerprint of probe row r over the probe table's own columns, as row_key computes the table's: the table's seed
+// and mask, the same per-column hashes, the same mixing by column position. false: a NULL component (a miss).
+__device__ __forceinline__ bool probe_fingerprint(const KeySpec& tk, const KeySpec& pk, int64_t r, uint64_t& h) {
+    uint64_t acc = tk.seed;
+    for (int i = 0; i < tk.ncols; ++i) {
+        const KeyCol& c = pk.cols[i];
+        if (!is_valid(c, r)) return false;
+        uint64_t ch;
+        if (c.spark_type == DQ_TYPE_STRING) {
+            int len;
+            const uint8_t* p = str_span(c, r, len);
+            ch = dev_xxh_bytes(p, len, tk.seed);
+        } else {
+            ch = xxh_long(canonical(c, r), tk.seed);
+        }
+        acc = mix64(acc + P64_1 * (uint64_t)(i + 1) + ch);
+    }
+    h = (acc == kEmpty ? kEmpty - 1 : acc) & tk.fp_mask;
+    return true;
+}
+
+// Probe row b (no NULL component) against row a of the table's source: fixed-width cells by their canonical values
+// (so BYTE .. LONG compare by value), strings by length and bytes.
+__device__ bool probe_rows_equal(const KeySpec& tk, int64_t a, const KeySpec& pk, int64_t b) {
+    for (int i = 0; i < tk.ncols; ++i) {
+        const KeyCol& ca = tk.cols[i];
+        const KeyCol& cb = pk.cols[i];
+        if (!is_valid(ca, a)) return false;
+        if (ca.spark_type == DQ_TYPE_STRING) {
+            int la, lb;
+            const uint8_t* pa = str_span(ca, a, la);
+            const uint8_t* pb = str_span(cb, b, lb);
+            if (la != lb) return false;
+            int k = 0;
+            for (; k + 8 <= la; k += 8)
+                if (dev_le64(pa + k) != dev_le64(pb + k)) return false;
+            if (k + 4 <= la) {
+                if (dev_le32(pa + k) != dev_le32(pb + k)) return false;
+                k += 4;
+            }
+            for (; k < la; ++k)
+                if (pa[k] != pb[k]) return false;
+        } else if (canonical(ca, a) != canonical(cb, b)) {
+            return false;
+        }
+    }
+    return true;
+}
+
+// The slot of key h in its region: its index, or -1 when an EMPTY slot ends the run first.
+__device__ __forceinline__ int64_t probe_find(const Slot* __restrict__ slots, int bits, uint64_t h) {
+    const uint64_t base = (h & ((1ull << bits) - 1)) * kRegion;
+    unsigned int p = region_probe(h);
+    for (int probe = 0; probe < kRegion; ++probe) {
+        const unsigned long long k = slots[base + p].key;
+        if (k == h) return (int64_t)(base + p);
+        if (k == kEmpty) return -1;
+        p = (p + 1) & (kRegion - 1);
+    }
+    return -1;
+}
+
+// One wave takes the 64 rows of a bitmap word; a lane decides its row, the ballot is the word (lanes past nrows vote
+// 0) and one lane stores it; the outcome bytes are the lanes' 64 consecutive bytes. `matched` adds the words'
+// popcounts: integers, so any grid gives the same count. (Several words per wave and step, their key loads and first
+// slot reads issued together, measured no faster: DESIGN.md 3h.)
+template <bool FAST>
+__global__ void __launch_bounds__(kFreqBlock)
+probe_kernel(LookupTable T, KeySpec P, const unsigned long long* __restrict__ reps, int64_t nrows, int64_t nwords,
+             unsigned long long* __restrict__ bits, uint8_t* __restrict__ outcome, unsigned long long* __restrict__ matched) {
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * (kFreqBlock / 64);
+    unsigned long long count = 0;
+    for (int64_t w = (int64_t)blockIdx.x * (kFreqBlock / 64) + (threadIdx.x >> 6); w < nwords; w += stride) {
+        const int64_t r = w * 64 + lane;
+        bool hit = false;
+        if (r < nrows) {
+            uint64_t h = kEmpty;
+            bool live;
+            if (FAST) {
+                live = is_valid(P.cols[0], r);
+                if (live) h = mix64(canonical(P.cols[0], r));
+                if (live && h == kEmpty) hit = T.sentinel > 0;  // the value kept in the side counter
+            } else {
+                live = probe_fingerprint(T.ks, P, r, h);
+            }
+            if (live && h != kEmpty) {
+                const int64_t at = probe_find(T.slots, T.bits, h);
+                // fast: mix64 is a bijection, an equal key is the value. general: a built table holds no two keys with
+                // one fingerprint, so the group's representative row decides
+                if (at >= 0) hit = FAST || probe_rows_equal(T.ks, (int64_t)reps[at], P, r);
+            }
+        }
+        const unsigned long long word = __ballot(hit);
+        if (bits && lane == 0) bits[w] = word;
+        if (outcome && r < nrows) outcome[r] = hit ? 1 : 0;
+        count += __popcll(word);
+    }
+    if (lane == 0 && count) atomicAdd(matched, count);
+}
+
 }  // namespace
 
 struct dq_ctx;  // defined in dq_api.cpp; only its device/stream are needed here
@@ -2121,6 +2226,7 @@ struct dq_freq_table {
     fx128 pre_ent = 0;
     unsigned int pre_nonfinite = 0;
     int32_t key_type = 0;   // Spark type of the (single) key column, or of the canonical keys of a pair-built table
+    int32_t key_scale[kMaxKeys] = {};  // decimal_scale of each key column (-1: unknown, a pair-built table's keys)
     int64_t num_rows_override = -1;  // tables built from (key, count) pairs carry the caller's numRows
     int64_t src_rows = -1;  // rows of the source columns (dq_frequencies_ex), -1 for pair-built / merged tables
     int64_t cached_n = -1;  // dq_freq_summarize memo (the table is immutable once built)
@@ -3344,6 +3450,7 @@ int dq_frequencies(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nro
 
 static int finish_frequencies(dq_ctx* ctx, dq_freq_table* t, int64_t nrows, const dq_freq_options* opt,
                               std::vector<void*>& staged, dq_freq_table** out);
+static int key_column(dq_ctx* ctx, const dq_column& col, int64_t nrows, KeyCol& kc, std::vector<void*>& staged);
 
 int dq_frequencies_ex(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, const int32_t* key_columns,
                       int nkeys, const dq_freq_options* opt, dq_freq_table** out) {
@@ -3353,7 +3460,6 @@ int dq_frequencies_ex(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t 
     *out = nullptr;
     const int dev = dq::ctx_device(ctx);
     DQ_CTX_HIP(ctx, hipSetDevice(dev));
-    hipStream_t s = dq::ctx_stream(ctx);
     dq_freq_table* t = new dq_freq_table();
     t->device = dev;
     t->src_rows = nrows;
@@ -3365,59 +3471,68 @@ int dq_frequencies_ex(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t 
     for (int i = 0; i < nkeys; ++i) {
         const int c = key_columns[i];
         if (c < 0 || c >= ncols || columns[c].length != nrows) {
+            cleanup();
             delete t;
             return dq::ctx_fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_frequencies: bad key column");
         }
-        const dq_column& col = columns[c];
-        KeyCol& kc = t->ks.cols[i];
-        kc.spark_type = col.spark_type;
-        kc.elem = elem_of(col.spark_type);
-        const bool off64 = col.spark_type == DQ_TYPE_STRING && (col.flags & DQ_COL_OFFSETS64);
-        kc.offsets64 = nullptr;
-        if (col.flags & DQ_COL_DEVICE) {
-            kc.values = col.values;
-            kc.validity = col.validity;
-            kc.offsets = off64 ? nullptr : col.offsets;
-            kc.offsets64 = off64 ? reinterpret_cast<const int64_t*>(col.offsets) : nullptr;
-        } else {
-            // stage host buffers (kept alive with the table: rows are re-read by verify / export)
-            const int64_t send = (!nrows || col.spark_type != DQ_TYPE_STRING)
-                                     ? 0
-                                     : (off64 ? reinterpret_cast<const int64_t*>(col.offsets)[nrows]
-                                              : (int64_t)col.offsets[nrows]);
-            size_t vbytes = col.spark_type == DQ_TYPE_STRING ? (size_t)send
-                                                              : (size_t)nrows * std::max(1, elem_size(kc.elem));
-            void* v = nullptr;
-            DQ_CTX_HIP(ctx, hipMalloc(&v, vbytes + 16));
-            staged.push_back(v);
-            if (vbytes) DQ_CTX_HIP(ctx, hipMemcpyAsync(v, col.values, vbytes, hipMemcpyHostToDevice, s));
-            kc.values = v;
-            if (col.validity) {
-                void* vd = nullptr;
-                const size_t nb = (size_t)(nrows + 7) / 8;
-                DQ_CTX_HIP(ctx, hipMalloc(&vd, nb + 8));
-                staged.push_back(vd);
-                if (nb) DQ_CTX_HIP(ctx, hipMemcpyAsync(vd, col.validity, nb, hipMemcpyHostToDevice, s));
-                kc.validity = (const uint8_t*)vd;
-            }
-            if (col.spark_type == DQ_TYPE_STRING) {
-                const size_t ow = off64 ? 8 : 4;
-                void* od = nullptr;
-                DQ_CTX_HIP(ctx, hipMalloc(&od, ((size_t)nrows + 1) * ow));
-                staged.push_back(od);
-                DQ_CTX_HIP(ctx, hipMemcpyAsync(od, col.offsets, ((size_t)nrows + 1) * ow, hipMemcpyHostToDevice, s));
-                kc.offsets = off64 ? nullptr : (const int32_t*)od;
-                kc.offsets64 = off64 ? (const int64_t*)od : nullptr;
-            }
-        }
-        if (kc.elem == ET_NONE && kc.spark_type != DQ_TYPE_STRING) {
+        t->key_scale[i] = columns[c].decimal_scale;
+        const int rc = key_column(ctx, columns[c], nrows, t->ks.cols[i], staged);
+        if (rc) {
             cleanup();
             delete t;
-            return dq::ctx_fail(ctx, DQ_ERR_UNSUPPORTED, "dq_frequencies: unsupported key type");
+            return rc == DQ_ERR_UNSUPPORTED ? dq::ctx_fail(ctx, rc, "dq_frequencies: unsupported key type") : rc;
         }
     }
     t->ks.ncols = nkeys;
     return finish_frequencies(ctx, t, nrows, opt, staged, out);
+}
+
+// `col` as a key column of `nrows` rows: a device column as it is; host buffers staged in HBM on the context's stream
+// and listed in `staged` (the caller frees them, also when this fails).
+static int key_column(dq_ctx* ctx, const dq_column& col, int64_t nrows, KeyCol& kc, std::vector<void*>& staged) {
+    kc.spark_type = col.spark_type;
+    kc.elem = elem_of(col.spark_type);
+    if (kc.elem == ET_NONE && kc.spark_type != DQ_TYPE_STRING) return DQ_ERR_UNSUPPORTED;
+    hipStream_t s = dq::ctx_stream(ctx);
+    const bool off64 = col.spark_type == DQ_TYPE_STRING && (col.flags & DQ_COL_OFFSETS64);
+    kc.offsets64 = nullptr;
+    if (col.flags & DQ_COL_DEVICE) {
+        kc.values = col.values;
+        kc.validity = col.validity;
+        kc.offsets = off64 ? nullptr : col.offsets;
+        kc.offsets64 = off64 ? reinterpret_cast<const int64_t*>(col.offsets) : nullptr;
+    } else {
+        // stage host buffers (a table keeps them alive: its rows are re-read by verify / export / probe)
+        const int64_t send = (!nrows || col.spark_type != DQ_TYPE_STRING)
+                                 ? 0
+                                 : (off64 ? reinterpret_cast<const int64_t*>(col.offsets)[nrows]
+                                          : (int64_t)col.offsets[nrows]);
+        size_t vbytes = col.spark_type == DQ_TYPE_STRING ? (size_t)send
+                                                          : (size_t)nrows * std::max(1, elem_size(kc.elem));
+        void* v = nullptr;
+        DQ_CTX_HIP(ctx, hipMalloc(&v, vbytes + 16));
+        staged.push_back(v);
+        if (vbytes) DQ_CTX_HIP(ctx, hipMemcpyAsync(v, col.values, vbytes, hipMemcpyHostToDevice, s));
+        kc.values = v;
+        if (col.validity) {
+            void* vd = nullptr;
+            const size_t nb = (size_t)(nrows + 7) / 8;
+            DQ_CTX_HIP(ctx, hipMalloc(&vd, nb + 8));
+            staged.push_back(vd);
+            if (nb) DQ_CTX_HIP(ctx, hipMemcpyAsync(vd, col.validity, nb, hipMemcpyHostToDevice, s));
+            kc.validity = (const uint8_t*)vd;
+        }
+        if (col.spark_type == DQ_TYPE_STRING) {
+            const size_t ow = off64 ? 8 : 4;
+            void* od = nullptr;
+            DQ_CTX_HIP(ctx, hipMalloc(&od, ((size_t)nrows + 1) * ow));
+            staged.push_back(od);
+            DQ_CTX_HIP(ctx, hipMemcpyAsync(od, col.offsets, ((size_t)nrows + 1) * ow, hipMemcpyHostToDevice, s));
+            kc.offsets = off64 ? nullptr : (const int32_t*)od;
+            kc.offsets64 = off64 ? (const int64_t*)od : nullptr;
+        }
+    }
+    return DQ_OK;
 }
 
 // The common tail of dq_frequencies_ex / dq_frequencies_parts: `t->ks.cols[0 .. nkeys)` are set up.
@@ -3504,6 +3619,7 @@ int dq_frequencies_parts(dq_ctx* ctx, const dq_column* parts, int nparts, int nc
                                 "dq_frequencies_parts: key parts must be device columns of one type, int32 offsets");
         }
         KeyCol& kc = t->ks.cols[i];
+        t->key_scale[i] = a->decimal_scale;
         kc.spark_type = a->spark_type;
         kc.elem = elem_of(a->spark_type);
         kc.values = a->values;
@@ -3817,6 +3933,7 @@ int dq_freq_from_pairs(dq_ctx* ctx, int32_t key_spark_type, const int64_t* keys,
     const int rc = dq_frequencies_ex(ctx, &col, 1, n, &key0, 1, &o, out);
     if (rc) return rc;
     (*out)->num_rows_override = num_rows;
+    (*out)->key_scale[0] = -1;
     (*out)->host_ctr.nulls = (unsigned long long)null_count;
     (*out)->cached_n = -1;
     return DQ_OK;
@@ -4021,6 +4138,95 @@ int dq_freq_row_bits(dq_ctx* ctx, const dq_freq_table* t, uint8_t* unique_bits_d
                        (unsigned long long*)unique_bits_dev, (unsigned long long*)part_bits_dev);
     DQ_CTX_HIP(ctx, hipGetLastError());
     DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
+    return DQ_OK;
+}
+
+// May a probe cell of `probe` be compared with a key cell of `key` by canonical value (or string bytes) under SQL '='?
+static bool probe_pair_ok(int32_t key, int32_t key_scale, int32_t probe, int32_t probe_scale) {
+    auto integral = [](int32_t t) { return t == DQ_TYPE_BYTE || t == DQ_TYPE_SHORT || t == DQ_TYPE_INT || t == DQ_TYPE_LONG; };
+    // '=' on floating cells (-0.0 = 0.0, NaN = NaN) is not the table's binary equality; wide decimals are no keys
+    if (probe == DQ_TYPE_FLOAT || probe == DQ_TYPE_DOUBLE || (elem_of(probe) == ET_NONE && probe != DQ_TYPE_STRING) ||
+        key == DQ_TYPE_FLOAT || key == DQ_TYPE_DOUBLE)
+        return false;
+    if (integral(key) && integral(probe)) return true;  // Spark promotes: canonical() sign-extends both
+    if (key != probe) return false;
+    return key != DQ_TYPE_DECIMAL || (key_scale >= 0 && key_scale == probe_scale);
+}
+
+int dq_freq_probe(dq_ctx* ctx, const dq_freq_table* t, const dq_column* columns, int ncols, int64_t nrows,
+                  const int32_t* key_columns, int nkeys, uint8_t* match_bits_dev, uint8_t* outcome_dev, int64_t* matched) {
+    if (!ctx || !t || !matched || nrows < 0 || nkeys <= 0 || (nrows > 0 && (!columns || !key_columns)))
+        return dq::ctx_fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_freq_probe: invalid arguments");
+    *matched = 0;
+    if (!ctx->subs.empty() || !t->parts.empty())
+        return dq::ctx_fail(ctx, DQ_ERR_UNSUPPORTED, "dq_freq_probe: needs a single-device context and table");
+    if (!t->fast && (t->src_rows < 0 || !t->reps))
+        return dq::ctx_fail(ctx, DQ_ERR_UNSUPPORTED, "dq_freq_probe: a table over general keys must still have its source rows");
+    if (t->ks.string_null_is_value)
+        return dq::ctx_fail(ctx, DQ_ERR_UNSUPPORTED, "dq_freq_probe: the table counts NULL as the string \"NullValue\"");
+    if (nkeys != t->ks.ncols)
+        return dq::ctx_fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_freq_probe: nkeys differs from the table's key columns");
+    if ((uintptr_t)match_bits_dev & 7) return dq::ctx_fail(ctx, DQ_ERR_ALIGNMENT, "dq_freq_probe: the bitmap must be 8-B aligned");
+    if (nrows == 0) return DQ_OK;
+    for (int i = 0; i < nkeys; ++i) {
+        const int c = key_columns[i];
+        if (c < 0 || c >= ncols || columns[c].length != nrows)
+            return dq::ctx_fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_freq_probe: bad key column");
+        const int32_t key_type = t->fast ? t->key_type : t->ks.cols[i].spark_type;
+        if (!probe_pair_ok(key_type, t->key_scale[i], columns[c].spark_type, columns[c].decimal_scale)) {
+            char msg[160];
+            snprintf(msg, sizeof(msg), "dq_freq_probe: key column %d: type %d (scale %d) against the table's %d (scale %d)", i,
+                     (int)columns[c].spark_type, (int)columns[c].decimal_scale, (int)key_type, (int)t->key_scale[i]);
+            return dq::ctx_fail(ctx, DQ_ERR_UNSUPPORTED, msg);
+        }
+    }
+    DQ_CTX_HIP(ctx, hipSetDevice(t->device));
+    hipStream_t s = dq::ctx_stream(ctx);
+    const int64_t nwords = (nrows + 63) >> 6;
+    if (!t->slots || !t->cap) {  // a table without slots holds no key: every row misses
+        if (match_bits_dev) DQ_CTX_HIP(ctx, hipMemsetAsync(match_bits_dev, 0, (size_t)nwords * 8, s));
+        if (outcome_dev) DQ_CTX_HIP(ctx, hipMemsetAsync(outcome_dev, 0, (size_t)nrows, s));
+        DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
+        return DQ_OK;
+    }
+    std::vector<void*> staged;
+    struct FreeStaged {  // after the stream's work: the kernel reads them
+        std::vector<void*>& v;
+        hipStream_t s;
+        ~FreeStaged() {
+            if (!v.empty()) (void)hipStreamSynchronize(s);
+            for (void* p : v) (void)hipFree(p);
+        }
+    } free_staged{staged, s};
+    KeySpec pk;
+    memset(&pk, 0, sizeof(pk));
+    pk.ncols = nkeys;
+    for (int i = 0; i < nkeys; ++i) {
+        const int rc = key_column(ctx, columns[key_columns[i]], nrows, pk.cols[i], staged);
+        if (rc) return rc == DQ_ERR_UNSUPPORTED ? dq::ctx_fail(ctx, rc, "dq_freq_probe: unsupported key type") : rc;
+    }
+    LookupTable T;
+    T.slots = t->slots;
+    T.ks = t->ks;
+    T.sentinel = t->host_ctr.sentinel;
+    T.bits = t->bits;
+    dq::ScratchBuffers buf(ctx);
+    unsigned long long* count = nullptr;
+    DQ_CTX_HIP(ctx, buf.alloc((void**)&count, 8));
+    DQ_CTX_HIP(ctx, hipMemsetAsync(count, 0, 8, s));
+    const int grid = scan_grid((uint64_t)nrows);
+    if (t->fast)
+        hipLaunchKernelGGL(probe_kernel<true>, dim3(grid), dim3(kFreqBlock), 0, s, T, pk, (const unsigned long long*)nullptr,
+                           nrows, nwords, (unsigned long long*)match_bits_dev, outcome_dev, count);
+    else
+        hipLaunchKernelGGL(probe_kernel<false>, dim3(grid), dim3(kFreqBlock), 0, s, T, pk, (const unsigned long long*)t->reps,
+                           nrows, nwords, (unsigned long long*)match_bits_dev, outcome_dev, count);
+    DQ_CTX_HIP(ctx, hipGetLastError());
+    ctx->kernel_launches[DQ_KERNEL_FREQ_PROBE]++;
+    unsigned long long got = 0;
+    DQ_CTX_HIP(ctx, hipMemcpyAsync(&got, count, 8, hipMemcpyDeviceToHost, s));
+    DQ_CTX_HIP(ctx, hipStreamSynchronize(s));
+    *matched = (int64_t)got;
     return DQ_OK;
 }
 

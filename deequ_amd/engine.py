@@ -218,6 +218,21 @@ class FrequencyTable:
         self.ctx.check(rc, "dq_freq_row_counts")
         return out[:n]
 
+    def probe(self, table, columns, want_bits=False, want_outcome=False):
+        """dq_freq_probe: does each row of `table` have its `columns` (paired by position with this table's key
+        columns) among this table's keys under SQL '='? Returns (matched rows, bitmap, outcome bytes): torch uint8
+        tensors in HBM, (nrows + 63) // 64 words and one 0/1 byte per row, or None where not asked for."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        n = table.nrows
+        names = list(table.columns)
+        bits = torch.zeros(max((n + 63) // 64, 1) * 8, dtype=torch.uint8, device=dev) if want_bits else None
+        outcome = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev) if want_outcome else None
+        matched = self.ctx.freq_probe(self.handle, [table[c].native() for c in names], n,
+                                      [names.index(c) for c in columns],
+                                      bits.data_ptr() if want_bits else None, outcome.data_ptr() if want_outcome else None)
+        return matched, bits, outcome
+
     def __del__(self):
         try:
             if self.handle:

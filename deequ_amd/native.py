@@ -62,7 +62,7 @@ FREQ_PATHS = ("fast", "fast_narrow", "fast_done", "exact", "partitioned", "sorte
               "split_buckets", "long_tuples")
 SCAN_KERNELS = ("striped", "striped_heavy", "heavy8", "heavy8_full", "bits", "pred_simple", "pred_vm", "regex",
                 "strings", "where_fused", "where_masks", "decimal128", "dict_counts", "dict_fold", "dict_decode",
-                "filter_validity", "row_outcomes")
+                "filter_validity", "row_outcomes", "freq_probe")
 
 # Every symbol include/dq.h declares (checked by tests/test_native_abi.py).
 EXPORTED_SYMBOLS = (
@@ -77,6 +77,7 @@ EXPORTED_SYMBOLS = (
     "dq_schema_validate", "dq_schema_launch_count", "dq_gather_rows", "dq_parse_int32", "dq_parse_decimal",
     "dq_parse_timestamp", "dq_split_rows", "dq_split_row_is_test", "dq_dec128_to_double",
     "dq_dict_scan", "dq_dict_counts", "dq_dict_decode", "dq_filter_validity", "dq_freq_row_bits", "dq_row_outcomes",
+    "dq_freq_probe",
 )
 
 
@@ -351,6 +352,8 @@ def load_library(path=None):
             "dq_filter_validity": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p,
                                            c_void_p]),
             "dq_freq_row_bits": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64]),
+            "dq_freq_probe": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p,
+                                      c_void_p]),
             "dq_row_outcomes": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                         c_int, c_uint32, c_void_p, c_void_p]),
         }
@@ -712,6 +715,20 @@ class Context:
         self._after_torch_stream()
         self.check(self.lib.dq_freq_row_bits(self.handle, table_handle, ctypes.c_void_p(unique_ptr),
                                              ctypes.c_void_p(part_ptr), int(nrows)), "dq_freq_row_bits")
+
+    def freq_probe(self, table_handle, columns, nrows, key_columns, bits_ptr=None, outcome_ptr=None):
+        """dq_freq_probe: the rows of `columns` (DqColumn list; `key_columns` index it, paired by position with the
+        table's key columns) against a frequency table under SQL '='. Optional device outputs: a bitmap
+        ((nrows + 63) // 64 words) and one 0/1 byte per row. Returns the number of matching rows."""
+        self._after_torch_stream()
+        col_arr = (DqColumn * max(len(columns), 1))(*columns)
+        keys = np.asarray(key_columns, dtype=np.int32)
+        matched = ctypes.c_int64(0)
+        self.check(self.lib.dq_freq_probe(self.handle, table_handle, col_arr, len(columns), int(nrows), keys.ctypes.data,
+                                          len(keys), ctypes.c_void_p(bits_ptr) if bits_ptr else None,
+                                          ctypes.c_void_p(outcome_ptr) if outcome_ptr else None, ctypes.byref(matched)),
+                   "dq_freq_probe")
+        return int(matched.value)
 
     def row_outcomes(self, columns, nrows, preds, terms, checks, flags=0):
         """dq_row_outcomes: `terms` (DqRowTerm) over `columns` / `preds` (DqPredicate) folded into the output buffers of

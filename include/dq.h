@@ -329,7 +329,8 @@ typedef enum dq_scan_kernel {
     DQ_KERNEL_DICT_DECODE = 14,   /* dq_dict_decode calls that copied bytes (a kept column handed on decoded)     */
     DQ_KERNEL_FILTER_VALIDITY = 15, /* filter_validity_kernel: a `where` ANDed into key-column validity bitmaps   */
     DQ_KERNEL_ROW_OUTCOMES = 16,  /* row_outcomes_kernel: the per-check row outcomes of one dq_row_outcomes call  */
-    DQ_KERNEL_COUNT = 17
+    DQ_KERNEL_FREQ_PROBE = 17,    /* probe_kernel: another table's rows against a frequency table (dq_freq_probe)  */
+    DQ_KERNEL_COUNT = 18
 } dq_scan_kernel;
 int64_t dq_scan_kernel_launches(const dq_ctx* ctx, int32_t kernel);
 
@@ -567,6 +568,22 @@ int dq_freq_row_counts(dq_ctx* ctx, const dq_freq_table* table, int64_t* counts,
  * nrows must be the table's source rows); DQ_ERR_ALIGNMENT for a misaligned bitmap. nrows == 0 launches nothing. */
 int dq_freq_row_bits(dq_ctx* ctx, const dq_freq_table* table, uint8_t* unique_bits_dev, uint8_t* part_bits_dev,
                      int64_t nrows);
+
+/* Semi-join probe. For each of `nrows` rows of `columns`: does its key (key_columns[0..nkeys), paired by
+ * position with the key columns `t` was built over) equal a key of `t` under SQL '='?
+ * match_bits_dev: optional device bitmap, 8-byte aligned, (nrows+63)/64 words, bits past nrows clear.
+ * outcome_dev:    optional device bytes, one 0/1 byte per row (the cells of a BOOLEAN column).
+ * matched:        the number of matching rows.
+ * A NULL component on either side never matches (the table's own grouping is null-safe; the probe is not). `t` is a
+ * single-device table; over general keys (strings, several columns) it must still have its source rows, which the
+ * probe compares with. The probe columns are host buffers (staged for the call) or DQ_COL_DEVICE. Type pairs: the
+ * same Spark type; any two of BYTE / SHORT / INT / LONG (by value); DECIMAL of one scale. DQ_ERR_UNSUPPORTED: a
+ * FLOAT / DOUBLE / DECIMAL128 pair or any other, a multi-device table or context, a DQ_FREQ_INCLUDE_NULLS table over
+ * one STRING column (it counts NULL as "NullValue"). DQ_ERR_INVALID_ARGUMENT: nkeys differs from the table's key
+ * count. nrows == 0 launches nothing. One launch (probe_kernel), counted under DQ_KERNEL_FREQ_PROBE. */
+int dq_freq_probe(dq_ctx*, const dq_freq_table* t, const dq_column* columns, int ncols, int64_t nrows,
+                  const int32_t* key_columns, int nkeys, uint8_t* match_bits_dev, uint8_t* outcome_dev,
+                  int64_t* matched);
 
 /* ApproxQuantile / ApproxQuantiles (A/ApproxQuantile.scala:28-103, A/ApproxQuantiles.scala:39-101): replaces the
  * per-row PercentileDigest.add of StatefulApproxQuantile.update (C/StatefulApproxQuantile.scala:65-72). Computes
