@@ -31,6 +31,12 @@ TYPE_BOOLEAN, TYPE_BYTE, TYPE_SHORT, TYPE_INT, TYPE_LONG, TYPE_FLOAT, TYPE_DOUBL
     TYPE_DATE, TYPE_TIMESTAMP, TYPE_DECIMAL = range(1, 12)
 TYPE_DECIMAL128 = 12  # 16-byte unscaled cells, precision 19..38 (DQ_TYPE_DECIMAL128)
 DEC128_TILE_ROWS = 1024  # rows one workgroup of the decimal128 scan takes per step (dq_internal.h kD128TileRows)
+CSV_TILE_BYTES = 16384  # bytes one workgroup of the CSV tokenizer takes (dq.h DQ_CSV_TILE_BYTES)
+CSV_CLASS_INT, CSV_CLASS_LONG, CSV_CLASS_DOUBLE, CSV_CLASS_BOOLEAN, CSV_CLASS_STRING = 1, 2, 4, 8, 16
+# dq_csv_refusal, by kind
+CSV_REFUSALS = {1: "a quote inside an unquoted field", 2: "text after a closing quote",
+                3: "a carriage return outside quotes that no line feed follows",
+                4: "an unterminated quoted field (an odd number of quotes)"}
 
 COL_DEVICE = 0x1
 COL_OFFSETS64 = 0x2  # STRING: int64 offsets (dq_frequencies only)
@@ -63,6 +69,8 @@ FREQ_PATHS = ("fast", "fast_narrow", "fast_done", "exact", "partitioned", "sorte
 SCAN_KERNELS = ("striped", "striped_heavy", "heavy8", "heavy8_full", "bits", "pred_simple", "pred_vm", "regex",
                 "strings", "where_fused", "where_masks", "decimal128", "dict_counts", "dict_fold", "dict_decode",
                 "filter_validity", "row_outcomes", "freq_probe")
+# the dq_scan_kernel entries after them: the kernels of the device CSV reader (dq_csv_index, dq_csv_column)
+CSV_KERNELS = ("csv_quotes", "csv_mark", "csv_rows", "csv_fields", "csv_column")
 
 # Every symbol include/dq.h declares (checked by tests/test_native_abi.py).
 EXPORTED_SYMBOLS = (
@@ -77,7 +85,7 @@ EXPORTED_SYMBOLS = (
     "dq_schema_validate", "dq_schema_launch_count", "dq_gather_rows", "dq_parse_int32", "dq_parse_decimal",
     "dq_parse_timestamp", "dq_split_rows", "dq_split_row_is_test", "dq_dec128_to_double",
     "dq_dict_scan", "dq_dict_counts", "dq_dict_decode", "dq_filter_validity", "dq_freq_row_bits", "dq_row_outcomes",
-    "dq_freq_probe",
+    "dq_freq_probe", "dq_csv_index", "dq_csv_field", "dq_csv_column", "dq_csv_free",
 )
 
 
@@ -105,6 +113,16 @@ class DqRowTerm(ctypes.Structure):
 
 class DqRowCheck(ctypes.Structure):
     _fields_ = [("pass_bits", ctypes.c_void_p), ("values", ctypes.c_void_p), ("validity", ctypes.c_void_p)]
+
+
+class DqCsvResult(ctypes.Structure):
+    _fields_ = [("nrows", ctypes.c_int64), ("refusal_kind", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("refusal_offset", ctypes.c_int64)]
+
+
+class DqCsvColumnReport(ctypes.Structure):
+    _fields_ = [("classes", ctypes.c_int32), ("reserved", ctypes.c_int32), ("valid", ctypes.c_int64),
+                ("ambiguous", ctypes.c_int64), ("first_ambiguous_row", ctypes.c_int64)]
 
 
 class DqConst(ctypes.Structure):
@@ -356,6 +374,12 @@ def load_library(path=None):
                                       c_void_p]),
             "dq_row_outcomes": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                         c_int, c_uint32, c_void_p, c_void_p]),
+            "dq_csv_index": (c_int, [c_void_p, c_void_p, c_int64, ctypes.c_int32, ctypes.c_int32, c_void_p, c_void_p,
+                                     c_void_p]),
+            "dq_csv_field": (c_int, [c_void_p, c_void_p, c_int64, ctypes.c_int32, c_void_p, c_void_p, c_void_p]),
+            "dq_csv_column": (c_int, [c_void_p, c_void_p, ctypes.c_int32, ctypes.c_int32, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]),
+            "dq_csv_free": (None, [c_void_p, c_void_p]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name)
@@ -745,6 +769,44 @@ class Context:
                                             len(terms), check_arr, len(checks), int(flags), tc, cc), "dq_row_outcomes")
         return ([(int(tc[2 * i]), int(tc[2 * i + 1])) for i in range(len(terms))],
                 [(int(cc[2 * i]), int(cc[2 * i + 1])) for i in range(len(checks))])
+
+    def csv_kernel_launches(self):
+        """{kernel name: launches so far} of the device CSV reader (the DQ_KERNEL_CSV_* entries)."""
+        return {name: int(self.lib.dq_scan_kernel_launches(self.handle, len(SCAN_KERNELS) + i))
+                for i, name in enumerate(CSV_KERNELS)}
+
+    def csv_index(self, bytes_ptr, nbytes, ncols, skip_records):
+        """dq_csv_index over device bytes: (handle or None for a refused file, DqCsvResult, [DqCsvColumnReport])."""
+        self._after_torch_stream()
+        handle = ctypes.c_void_p(None)
+        res = DqCsvResult()
+        reports = (DqCsvColumnReport * max(int(ncols), 1))()
+        self.check(self.lib.dq_csv_index(self.handle, ctypes.c_void_p(bytes_ptr), int(nbytes), int(ncols),
+                                         int(skip_records), ctypes.byref(handle), ctypes.byref(res), reports),
+                   "dq_csv_index")
+        return handle.value, res, [reports[i] for i in range(int(ncols))]
+
+    def csv_field(self, handle, row, col):
+        """dq_csv_field: (start, unquoted length, escaped) of one field of an index."""
+        start, length, escaped = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int32(0)
+        self.check(self.lib.dq_csv_field(self.handle, ctypes.c_void_p(handle), int(row), int(col), ctypes.byref(start),
+                                         ctypes.byref(length), ctypes.byref(escaped)), "dq_csv_field")
+        return int(start.value), int(length.value), bool(escaped.value)
+
+    def csv_column(self, handle, col, spark_type, values_ptr, validity_ptr, offsets_ptr=None):
+        """dq_csv_column into caller-owned device buffers; returns the bytes of a string column."""
+        self._after_torch_stream()
+        nbytes = ctypes.c_int64(0)
+        self.check(self.lib.dq_csv_column(self.handle, ctypes.c_void_p(handle), int(col), int(spark_type),
+                                          ctypes.c_void_p(values_ptr) if values_ptr else None,
+                                          ctypes.c_void_p(validity_ptr) if validity_ptr else None,
+                                          ctypes.c_void_p(offsets_ptr) if offsets_ptr else None, ctypes.byref(nbytes)),
+                   "dq_csv_column")
+        return int(nbytes.value)
+
+    def csv_free(self, handle):
+        if handle:
+            self.lib.dq_csv_free(self.handle, ctypes.c_void_p(handle))
 
     def split_rows(self, nrows, row0, seed, test_ratio, train_ptr, test_ptr):
         """dq_split_rows into two device bitmaps (either pointer may be None); returns (num_train, num_test)."""

@@ -8,6 +8,7 @@ repeated runs read device-resident data, as the benchmark does.
 """
 import csv
 import math
+import os
 import re
 from collections import OrderedDict
 
@@ -698,8 +699,13 @@ class Table:
         return cls(cols)
 
     @classmethod
-    def from_csv(cls, path, header=True, infer_schema=True):
-        """CSV -> Table with Spark 2.2 CSV `inferSchema` typing (empty field = null)."""
+    def from_csv(cls, path, header=True, infer_schema=True, device=None):
+        """CSV -> Table with Spark 2.2 CSV `inferSchema` typing (empty field = null). `device=d`: the file's bytes are
+        uploaded once and tokenized, typed and parsed on GPU d into a device-resident Table (`_from_csv_device`): the
+        same names, types, validity and cells as the host path, or a ValueError for input the host path reads
+        leniently."""
+        if device is not None:
+            return _from_csv_device(cls, path, header, infer_schema, device)
         with open(path, newline="") as f:
             rows = list(csv.reader(f))
         names = rows[0] if header else ["_c%d" % i for i in range(len(rows[0]))]
@@ -943,6 +949,114 @@ def _csv_field_type(x):
     if x.lower() in ("true", "false"):
         return N.TYPE_BOOLEAN
     return N.TYPE_STRING
+
+
+def _csv_type_of_classes(classes):
+    """The column type of the OR of its fields' classes (N.CSV_CLASS_*): what _csv_infer's sequential fold gives for
+    any order of fields of those classes. A subset of {INT, LONG, DOUBLE} is its widest member, {BOOLEAN} is BOOLEAN,
+    anything else (and no field at all) is STRING."""
+    if classes and not classes & ~(N.CSV_CLASS_INT | N.CSV_CLASS_LONG | N.CSV_CLASS_DOUBLE):
+        return N.TYPE_DOUBLE if classes & N.CSV_CLASS_DOUBLE else \
+            N.TYPE_LONG if classes & N.CSV_CLASS_LONG else N.TYPE_INT
+    return N.TYPE_BOOLEAN if classes == N.CSV_CLASS_BOOLEAN else N.TYPE_STRING
+
+
+def _csv_first_record(raw):
+    """(fields, complete) of the first record of a file's first bytes (the header), read as dq_csv_index reads
+    records: up to the first LF outside quotes (`complete`: there is one in `raw`), a CR before it dropped, split at
+    the commas outside quotes, quoted fields unquoted. A record of zero bytes has no fields."""
+    end, quotes, at = None, 0, 0
+    while end is None:
+        nl = raw.find(b"\n", at)
+        if nl < 0:
+            break
+        quotes += raw.count(b'"', at, nl)
+        if quotes % 2 == 0:
+            end = nl
+        at = nl + 1
+    rec = raw if end is None else raw[:end]
+    if end is not None and rec.endswith(b"\r"):
+        rec = rec[:-1]
+    fields, start, inside = [], 0, False
+    for i in range(len(rec) + 1 if rec else 0):
+        c = rec[i:i + 1]
+        if c == b'"':
+            inside = not inside
+        if i == len(rec) or (c == b"," and not inside):
+            f = rec[start:i]
+            if f[:1] == b'"':
+                f = f[1:-1].replace(b'""', b'"')
+            fields.append(f.decode("utf-8", errors="replace"))
+            start = i + 1
+    return fields, end is not None
+
+
+def _from_csv_device(cls, path, header, infer_schema, device):
+    """Table.from_csv on the GPU (csv.hip): one upload of the file's bytes, then dq_csv_index (records, field spans,
+    per-column classes, refusals) and one dq_csv_column per column into torch buffers laid out as `to_device` lays
+    them out. Only the header record and, for a column with ambiguous fields, one field are read on the host."""
+    nbytes = os.path.getsize(path)
+    if nbytes == 0:
+        raise ValueError("%s: an empty file has no header and no rows" % path)
+    if nbytes >= 2 ** 31:
+        raise ValueError("%s: %d bytes: the device reader takes files below 2^31 bytes" % (path, nbytes))
+    raw = np.fromfile(path, dtype=np.uint8)
+    head = 1 << 16
+    while True:
+        first, complete = _csv_first_record(raw[:head].tobytes())
+        if complete or head >= len(raw):
+            break
+        head *= 4
+    names = first if header else ["_c%d" % i for i in range(len(first))]
+    import torch
+    from . import engine
+    dev = device if isinstance(device, torch.device) else torch.device("cuda", int(device))
+    ctx = engine.ctx()
+    if ctx.multi or ctx.device != dev.index:
+        ctx = N.context(dev.index)
+    data = torch.from_numpy(raw).to(dev)
+    handle, res, reports = ctx.csv_index(data.data_ptr(), len(raw), max(len(names), 1), 1 if header else 0)
+    if res.refusal_kind:
+        raise ValueError("%s: %s at byte %d: csv.reader reads this leniently, the device reader refuses it"
+                         % (path, N.CSV_REFUSALS[res.refusal_kind], res.refusal_offset))
+    try:
+        if not names:
+            raise ValueError("%s: the first record has no fields" % path)
+        n = int(res.nrows)
+        cols = []
+        for j, name in enumerate(names):
+            rep = reports[j]
+            t = _csv_type_of_classes(rep.classes) if infer_schema else N.TYPE_STRING
+            if infer_schema and rep.ambiguous and not rep.classes & N.CSV_CLASS_STRING:
+                # Python's \d and $ accept more than ASCII digits: the host types the first such field
+                start, length, escaped = ctx.csv_field(handle, rep.first_ambiguous_row, j)
+                if escaped:
+                    field = raw[start:start + 2 * length].tobytes().replace(b'""', b'"')[:length]
+                else:
+                    field = raw[start:start + length].tobytes()
+                if _csv_field_type(field.decode("utf-8")) != N.TYPE_STRING:
+                    raise ValueError("%s: column %r: row %d holds %r, which the host path reads as a number or boolean "
+                                     "but the device does not parse; infer_schema=False loads the column as strings"
+                                     % (path, name, rep.first_ambiguous_row, field.decode("utf-8")))
+                t = N.TYPE_STRING
+            col = Column(name, t, None, None, length=n)
+            d = {}
+            if rep.valid < n:
+                d["validity"] = torch.zeros(max((n + 63) // 64, 1) * 8, dtype=torch.uint8, device=dev)
+            vptr = d["validity"].data_ptr() if "validity" in d else None
+            if t == N.TYPE_STRING:
+                d["offsets"] = torch.empty(n + 1, dtype=torch.int32, device=dev)
+                total = ctx.csv_column(handle, j, t, None, vptr, d["offsets"].data_ptr())
+                d["values"] = torch.empty(total + 16, dtype=torch.uint8, device=dev)
+                ctx.csv_column(handle, j, t, d["values"].data_ptr(), None, d["offsets"].data_ptr())
+            else:
+                d["values"] = torch.empty(n * np.dtype(NUMPY_OF[t]).itemsize, dtype=torch.uint8, device=dev)
+                ctx.csv_column(handle, j, t, d["values"].data_ptr(), vptr)
+            col.device = d
+            cols.append(col)
+    finally:
+        ctx.csv_free(handle)
+    return cls(cols)
 
 
 def _concat_host(parts):

@@ -330,7 +330,12 @@ typedef enum dq_scan_kernel {
     DQ_KERNEL_FILTER_VALIDITY = 15, /* filter_validity_kernel: a `where` ANDed into key-column validity bitmaps   */
     DQ_KERNEL_ROW_OUTCOMES = 16,  /* row_outcomes_kernel: the per-check row outcomes of one dq_row_outcomes call  */
     DQ_KERNEL_FREQ_PROBE = 17,    /* probe_kernel: another table's rows against a frequency table (dq_freq_probe)  */
-    DQ_KERNEL_COUNT = 18
+    DQ_KERNEL_CSV_QUOTES = 18,    /* csv_quotes_kernel: quote counts per tile of a CSV file (dq_csv_index)         */
+    DQ_KERNEL_CSV_MARK = 19,      /* csv_mark_kernel: terminator / delimiter bitmaps and the refusal checks        */
+    DQ_KERNEL_CSV_ROWS = 20,      /* csv_rows_kernel: record starts                                                */
+    DQ_KERNEL_CSV_FIELDS = 21,    /* csv_fields_kernel: field spans, classes and ambiguity reports                 */
+    DQ_KERNEL_CSV_COLUMN = 22,    /* the per-column kernels of dq_csv_column (lengths, gather, typed parse)        */
+    DQ_KERNEL_COUNT = 23
 } dq_scan_kernel;
 int64_t dq_scan_kernel_launches(const dq_ctx* ctx, int32_t kernel);
 
@@ -714,6 +719,70 @@ int dq_gather_rows(dq_ctx* ctx, const dq_column* column, int64_t nrows, const ui
 int dq_parse_int32(const uint8_t* s, int32_t n, int32_t* out);
 int dq_parse_decimal(const uint8_t* s, int32_t n, int32_t precision, int32_t scale, int64_t* out);
 int dq_parse_timestamp(const uint8_t* program, int32_t program_len, const uint8_t* s, int32_t n, int64_t* out);
+
+/* ---- CSV files parsed on the device (Table.from_csv(path, device=...)) -----------------------------------------------
+ * The dialect is Python's csv.reader default: ',' delimiter, '"' quote, a doubled quote as the escape. With q(i) the
+ * number of '"' bytes before byte i, a byte is outside quotes when q(i) is even; outside quotes ',' ends a field and LF
+ * or CR LF ends a record. A field whose first byte is '"' is quoted: its value is the bytes between the enclosing
+ * quotes with "" collapsed. A record of zero bytes is a row of NULL cells; the bytes after the last terminator are a
+ * record when there is at least one; an empty field is NULL, a missing field is NULL, fields past ncols are dropped.
+ * Input is taken to be UTF-8 and is not validated.
+ *
+ * Input that csv.reader reads leniently is refused: the call returns DQ_OK with refusal_kind != 0, the byte offset of
+ * the first occurrence (the smallest offset; the lower kind on a tie) and no handle. */
+#define DQ_CSV_TILE_BYTES 16384 /* bytes one workgroup of the tokenizer takes */
+typedef enum dq_csv_refusal {
+    DQ_CSV_OK = 0,
+    DQ_CSV_QUOTE_IN_FIELD = 1,     /* an opening quote (q even) not at the start of the file or after ',', LF, '"'  */
+    DQ_CSV_TEXT_AFTER_QUOTE = 2,   /* a closing quote (q odd) not before the end of the file, ',', LF, CR LF, '"'   */
+    DQ_CSV_LONE_CR = 3,            /* a CR outside quotes that no LF follows                                       */
+    DQ_CSV_UNTERMINATED_QUOTE = 4  /* an odd number of quotes; the offset is that of the file's last quote          */
+} dq_csv_refusal;
+/* The class of one field's value, the host's _csv_field_type (Spark 2.2 CSVInferSchema): [+-]?[0-9]+ is INT, LONG or
+ * DOUBLE by value range; [+-]?([0-9]+\.?[0-9]*|\.[0-9]+)([eE][+-]?[0-9]+)? and the literals NaN, Infinity, -Infinity
+ * are DOUBLE; a case-insensitive true / false is BOOLEAN; anything else is STRING. A value with a byte >= 0x80 or
+ * ending in LF is AMBIGUOUS (Python's \d and $ accept more than ASCII digits): it is counted, not classified. */
+#define DQ_CSV_CLASS_INT 1
+#define DQ_CSV_CLASS_LONG 2
+#define DQ_CSV_CLASS_DOUBLE 4
+#define DQ_CSV_CLASS_BOOLEAN 8
+#define DQ_CSV_CLASS_STRING 16
+typedef struct dq_csv dq_csv; /* the index of one file: 8 bytes of device memory per (row, column) */
+typedef struct dq_csv_result {
+    int64_t nrows;          /* records after the skipped ones */
+    int32_t refusal_kind;   /* dq_csv_refusal */
+    int32_t reserved;
+    int64_t refusal_offset; /* byte offset of the refusal */
+} dq_csv_result;
+typedef struct dq_csv_column_report {
+    int32_t classes;             /* OR of DQ_CSV_CLASS_* over the column's unambiguous non-NULL fields */
+    int32_t reserved;
+    int64_t valid;               /* non-NULL fields */
+    int64_t ambiguous;           /* ambiguous fields */
+    int64_t first_ambiguous_row; /* the smallest row holding one, -1 without */
+} dq_csv_column_report;
+/* Index the nbytes (1 .. 2^31 - 1) of a file at `bytes` (device memory, 16-B aligned, no padding needed; it must stay
+ * alive and unchanged until dq_csv_free): records, the first ncols field spans of every record after the first
+ * skip_records (0 or 1: the header), and `reports` (ncols entries, host). Kernel launches do not depend on the input:
+ * one each of DQ_KERNEL_CSV_QUOTES, _MARK, _ROWS and _FIELDS (the last two not for a refused file, the last not for a
+ * file without rows). Single-device contexts only (DQ_ERR_UNSUPPORTED otherwise). */
+int dq_csv_index(dq_ctx* ctx, const uint8_t* bytes, int64_t nbytes, int32_t ncols, int32_t skip_records, dq_csv** out,
+                 dq_csv_result* result, dq_csv_column_report* reports);
+/* One field of the index: the offset of its first content byte (after an opening quote), its unquoted length (0 =
+ * NULL) and whether the content holds "" pairs to collapse. Host outputs; one 8-byte copy from the device. */
+int dq_csv_field(dq_ctx* ctx, const dq_csv* csv, int64_t row, int32_t col, int64_t* start, int32_t* length,
+                 int32_t* escaped);
+/* Column `col` as spark_type. out_validity (device, ceil(nrows / 64) x 8 B, may be NULL) receives every word, bits at
+ * and past nrows 0. DQ_TYPE_STRING: two calls, as dq_gather_rows: with out_values == NULL, writes out_offsets
+ * (nrows + 1 int32, device), out_validity and *out_bytes; then with out_values (>= *out_bytes + 16 bytes) and the same
+ * out_offsets, writes the unquoted bytes and zeroes the 16 bytes after them. DQ_TYPE_INT / LONG / DOUBLE / BOOLEAN
+ * (int32 / int64 / double / one 0-1 byte per row, NULL cells 0): one call; every non-NULL field must be of a class the
+ * type holds (reports). A DOUBLE is the correctly rounded value (dq_parse.h); a cell whose rounding the device cannot
+ * decide (more than 19 significant digits on a boundary) fails the call with DQ_ERR_UNSUPPORTED. One launch per call,
+ * counted under DQ_KERNEL_CSV_COLUMN. */
+int dq_csv_column(dq_ctx* ctx, const dq_csv* csv, int32_t col, int32_t spark_type, void* out_values, uint8_t* out_validity,
+                  int32_t* out_offsets, int64_t* out_bytes);
+void dq_csv_free(dq_ctx* ctx, dq_csv* csv);
 
 /* Train / test row split (ConstraintSuggestionRunner.useTrainTestSplitWithTestsetRatio). Row r of this call is global
  * row g = row0 + r. h = XXH64 of the 8 little-endian bytes of g with seed `seed`: Spark's XXH64.hashLong(g, seed), the
