@@ -716,11 +716,15 @@ __device__ __forceinline__ void accumulate_int(IAcc& a, const uint64_t (&v)[8], 
         // Deviations from a shift c, then one reciprocal: with c = the running mean (or, on the lane's first
         // batch, any value of the batch) the Chan merge of (cnt, mean_b, m2_b) into (n, mean, m2) collapses to
         // mean' = c + S1 / n', m2' = m2 + S2 - S1^2 / n' (S1, S2: sums of the shifted deviations; n' = n + cnt).
+        // The first-batch pick sits behind a wave-uniform branch: as a plain per-lane `if` it is if-converted and
+        // its 8 compares + 16 selects run on every tile for something that happens once per lane.
         double c = a.mean;
-        if (a.n == 0) {
-            c = 0.0;
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(a.n == 0) != 0, 0)) {
+            if (a.n == 0) {
+                c = 0.0;
 #pragma unroll
-            for (int k = 7; k >= 0; --k) c = ((m >> k) & 1u) ? xd[k] : c;
+                for (int k = 7; k >= 0; --k) c = ((m >> k) & 1u) ? xd[k] : c;
+            }
         }
         double s1 = 0.0, s2 = 0.0;
 #pragma unroll
@@ -916,7 +920,8 @@ __device__ __forceinline__ void hll_update(uint32_t* regs, const uint64_t (&v)[8
 // after them and vector loads retire in order, so the wait in front of the fold drains that prefetch too
 // (s_waitcnt vmcnt(0)): a wave has one tile in flight and none while it folds; the overlap comes from the
 // 3 waves per SIMD. A true two-set pipeline (both sets issued ahead, counted waits, loop unrolled by two)
-// was built and measured no faster on either C2 launch (tried and dropped).
+// was built and measured no faster on either C2 launch (tried and dropped). The loop below is unrolled
+// by two only so that the two value register sets swap roles instead of being copied; the waits are unchanged.
 // ------------------------------------------------------------------------------------------------
 template <int NC, bool F0, bool F1>
 struct BlockRed {
@@ -1040,11 +1045,15 @@ scan_values_kernel(const SlotDesc* __restrict__ slots, const int32_t* __restrict
                 if (NC > 1) load_values<P, F1>(c1, tn * kTileRows, tid, true, nrows, yn);
             }
             fold(t * kTileRows, true, x, y);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                x[k] = xn[k];
-                if (NC > 1) y[k] = yn[k];
+            // Second half of the by-two iteration: tile tn out of (xn, yn) while tile tn + G loads into (x, y). The
+            // two register sets swap roles instead of being copied (8 v_mov_b64 per tile and column).
+            if (tn >= nfull) break;
+            t = tn;
+            if (t + G < nfull) {
+                load_values<P, F0>(c0, (t + G) * kTileRows, tid, true, nrows, x);
+                if (NC > 1) load_values<P, F1>(c1, (t + G) * kTileRows, tid, true, nrows, y);
             }
+            fold(t * kTileRows, true, xn, yn);
         }
         // The partial last tile (if any) goes to the workgroup next in the interleave.
         if (nfull < ntiles && blockIdx.x == nfull % G) {

@@ -49,6 +49,7 @@ OP2(k_fma64, "v_fma_f64 %0, %0, %0, %0")
 OP2(k_add64f, "v_add_f64 %0, %0, %0")
 OP2(k_min64f, "v_min_f64 %0, %0, %0")
 OP2(k_cvt64, "v_cvt_f64_i32 %0, %1")
+OP2(k_cvt64u, "v_cvt_f64_u32 %0, %1")
 
 typedef void (*kfn)(uint32_t*, uint32_t);
 
@@ -64,7 +65,7 @@ int main() {
         {"v_add_u32", k_add}, {"v_xor_b32", k_xor}, {"v_mul_lo_u32", k_mullo}, {"v_mul_hi_u32", k_mulhi},
         {"v_alignbit_b32", k_alignbit}, {"v_ffbh_u32", k_ffbh}, {"v_mad_u64_u32", k_mad64},
         {"v_lshlrev_b64", k_lshl64}, {"v_fma_f64", k_fma64}, {"v_add_f64", k_add64f}, {"v_min_f64", k_min64f},
-        {"v_cvt_f64_i32", k_cvt64}};
+        {"v_cvt_f64_i32", k_cvt64}, {"v_cvt_f64_u32", k_cvt64u}};
     hipEvent_t a, b;
     hipEventCreate(&a);
     hipEventCreate(&b);
