@@ -315,7 +315,7 @@ def _masked_column(col, dev_bitmap, host_bitmap):
     in HBM) where the column is device-resident, `host_bitmap` (numpy) where it has host buffers."""
     from .table import Column, DictColumn
     if isinstance(col, DictColumn):
-        out = DictColumn(col.name, col.indices, host_bitmap, col.dictionary)
+        out = DictColumn(col.name, col.indices, host_bitmap, col.dictionary, length=col.length)
         if col.dict_device is not None:
             out.dict_device = dict(col.dict_device, validity=dev_bitmap)
         return out
@@ -399,7 +399,7 @@ class FilterCache:
             for n, b in zip(part, bitmaps):
                 col = data[n]
                 # copied back (n / 8 bytes) where the column has a host side: its cells are then read on the host
-                host_side = isinstance(col, DictColumn) or col.values is not None
+                host_side = col.indices is not None if isinstance(col, DictColumn) else col.values is not None
                 out[n] = _masked_column(col, b, b.cpu().numpy() if host_side else None)
         return out, kept
 

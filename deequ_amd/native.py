@@ -71,6 +71,10 @@ SCAN_KERNELS = ("striped", "striped_heavy", "heavy8", "heavy8_full", "bits", "pr
                 "filter_validity", "row_outcomes", "freq_probe")
 # the dq_scan_kernel entries after them: the kernels of the device CSV reader (dq_csv_index, dq_csv_column)
 CSV_KERNELS = ("csv_quotes", "csv_mark", "csv_rows", "csv_fields", "csv_column")
+# and after those: the kernels that bring uploaded Arrow buffers into the column layout (dq_ingest_*)
+INGEST_KERNELS = ("ingest_validity", "ingest_bool", "ingest_offsets", "ingest_convert", "ingest_indices")
+# dq_ingest_kind
+INGEST_DECIMAL_LOW, INGEST_DECIMAL_WIDE, INGEST_TIME_MUL, INGEST_TIME_DIV = 1, 2, 3, 4
 
 # Every symbol include/dq.h declares (checked by tests/test_native_abi.py).
 EXPORTED_SYMBOLS = (
@@ -86,6 +90,7 @@ EXPORTED_SYMBOLS = (
     "dq_parse_timestamp", "dq_split_rows", "dq_split_row_is_test", "dq_dec128_to_double",
     "dq_dict_scan", "dq_dict_counts", "dq_dict_decode", "dq_filter_validity", "dq_freq_row_bits", "dq_row_outcomes",
     "dq_freq_probe", "dq_csv_index", "dq_csv_field", "dq_csv_column", "dq_csv_free",
+    "dq_ingest_bits", "dq_ingest_offsets", "dq_ingest_convert", "dq_ingest_indices",
 )
 
 
@@ -123,6 +128,16 @@ class DqCsvResult(ctypes.Structure):
 class DqCsvColumnReport(ctypes.Structure):
     _fields_ = [("classes", ctypes.c_int32), ("reserved", ctypes.c_int32), ("valid", ctypes.c_int64),
                 ("ambiguous", ctypes.c_int64), ("first_ambiguous_row", ctypes.c_int64)]
+
+
+class DqIngestPiece(ctypes.Structure):
+    """dq_ingest_piece: the bits of one slice of an Arrow chunk (device memory) and its place in the output."""
+    _fields_ = [("src", ctypes.c_void_p), ("src_bytes", ctypes.c_int64), ("src_bit0", ctypes.c_int64),
+                ("rows", ctypes.c_int64), ("out_row0", ctypes.c_int64)]
+
+
+class DqIngestIndexReport(ctypes.Structure):
+    _fields_ = [("bad_row", ctypes.c_int64), ("bad_index", ctypes.c_int64), ("null_rows", ctypes.c_int64)]
 
 
 class DqConst(ctypes.Structure):
@@ -380,6 +395,13 @@ def load_library(path=None):
             "dq_csv_column": (c_int, [c_void_p, c_void_p, ctypes.c_int32, ctypes.c_int32, c_void_p, c_void_p, c_void_p,
                                       c_void_p]),
             "dq_csv_free": (None, [c_void_p, c_void_p]),
+            "dq_ingest_bits": (c_int, [c_void_p, c_void_p, ctypes.c_int32, c_int64, ctypes.c_int32, c_void_p]),
+            "dq_ingest_offsets": (c_int, [c_void_p, c_void_p, c_int64, ctypes.c_int32, c_int64, c_int64, ctypes.c_int32,
+                                          c_void_p, c_void_p]),
+            "dq_ingest_convert": (c_int, [c_void_p, ctypes.c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64,
+                                          c_int64, c_void_p]),
+            "dq_ingest_indices": (c_int, [c_void_p, c_void_p, c_int64, ctypes.c_int32, ctypes.c_int32, c_void_p, c_int64,
+                                          c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
         }
         for name, (res, args) in sig.items():
             f = getattr(lib, name)
@@ -807,6 +829,55 @@ class Context:
     def csv_free(self, handle):
         if handle:
             self.lib.dq_csv_free(self.handle, ctypes.c_void_p(handle))
+
+    def ingest_kernel_launches(self):
+        """{kernel name: launches so far} of the Arrow ingest (the DQ_KERNEL_INGEST_* entries)."""
+        return {name: int(self.lib.dq_scan_kernel_launches(self.handle, len(SCAN_KERNELS) + len(CSV_KERNELS) + i))
+                for i, name in enumerate(INGEST_KERNELS)}
+
+    def ingest_bits(self, pieces, nrows, to_bytes, out_ptr):
+        """dq_ingest_bits: `pieces` = [(src_ptr or None, src_bytes, src_bit0, rows)] in row order -> the validity
+        words (to_bytes False) or one byte per row (True) at out_ptr."""
+        self._after_torch_stream()
+        arr = (DqIngestPiece * max(len(pieces), 1))()
+        at = 0
+        for k, (src, nbytes, bit0, rows) in enumerate(pieces):
+            arr[k].src, arr[k].src_bytes, arr[k].src_bit0, arr[k].rows, arr[k].out_row0 = src, nbytes, bit0, rows, at
+            at += rows
+        self.check(self.lib.dq_ingest_bits(self.handle, arr, len(pieces), int(nrows), 1 if to_bytes else 0,
+                                           ctypes.c_void_p(out_ptr)), "dq_ingest_bits")
+
+    def ingest_offsets(self, src_ptr, src_bytes, src_width, rows, base, write_last, out_ptr):
+        """dq_ingest_offsets for one piece; True when a rebased offset left [0, 2^31)."""
+        self._after_torch_stream()
+        flag = ctypes.c_int32(0)
+        self.check(self.lib.dq_ingest_offsets(self.handle, ctypes.c_void_p(src_ptr), int(src_bytes), int(src_width),
+                                              int(rows), int(base), 1 if write_last else 0, ctypes.c_void_p(out_ptr),
+                                              ctypes.byref(flag)), "dq_ingest_offsets")
+        return bool(flag.value)
+
+    def ingest_convert(self, kind, src_ptr, src_bytes, validity, rows, param, out_ptr):
+        """dq_ingest_convert for one piece; `validity` = (ptr, bytes, bit0) or None."""
+        self._after_torch_stream()
+        vptr, vbytes, vbit0 = validity or (None, 0, 0)
+        self.check(self.lib.dq_ingest_convert(self.handle, int(kind), ctypes.c_void_p(src_ptr), int(src_bytes),
+                                              ctypes.c_void_p(vptr) if vptr else None, int(vbytes), int(vbit0), int(rows),
+                                              int(param), ctypes.c_void_p(out_ptr)), "dq_ingest_convert")
+
+    def ingest_indices(self, src_ptr, src_bytes, width, signed, validity, rows, n_dict, dict_validity_ptr, out_ptr,
+                       out_validity_ptr):
+        """dq_ingest_indices for one piece: (bad_row or -1, bad_index, null_rows)."""
+        self._after_torch_stream()
+        vptr, vbytes, vbit0 = validity or (None, 0, 0)
+        rep = DqIngestIndexReport()
+        self.check(self.lib.dq_ingest_indices(self.handle, ctypes.c_void_p(src_ptr), int(src_bytes), int(width),
+                                              1 if signed else 0, ctypes.c_void_p(vptr) if vptr else None, int(vbytes),
+                                              int(vbit0), int(rows), int(n_dict),
+                                              ctypes.c_void_p(dict_validity_ptr) if dict_validity_ptr else None,
+                                              ctypes.c_void_p(out_ptr),
+                                              ctypes.c_void_p(out_validity_ptr) if out_validity_ptr else None,
+                                              ctypes.byref(rep)), "dq_ingest_indices")
+        return int(rep.bad_row), int(rep.bad_index), int(rep.null_rows)
 
     def split_rows(self, nrows, row0, seed, test_ratio, train_ptr, test_ptr):
         """dq_split_rows into two device bitmaps (either pointer may be None); returns (num_train, num_test)."""

@@ -319,15 +319,17 @@ class DictColumn(Column):
     dq_dict_counts). Every consumer that does not know the class sees a plain STRING column: `values`, `offsets`,
     `device` and `native()` are those of `decoded()`, built on first use (on the device for a device column)."""
 
-    def __init__(self, name, indices, validity, dictionary):
+    def __init__(self, name, indices, validity, dictionary, length=None):
         self.name = name
         self.spark_type = N.TYPE_STRING
-        self.indices = np.ascontiguousarray(indices, dtype=np.int32)
+        # None (with `length`): a column ingested on the device (from_arrow(device=...)), whose indices and validity
+        # live in dict_device only; its cells are read through decoded()
+        self.indices = None if indices is None else np.ascontiguousarray(indices, dtype=np.int32)
         self.validity = validity
         self.dictionary = dictionary
         self.decimal_precision = 0
         self.decimal_scale = 0
-        self.length = len(self.indices)
+        self.length = len(self.indices) if indices is not None else int(length)
         self.dict_device = None  # torch tensors once resident: indices, validity, dict_values, dict_offsets, dict_validity
         self.tz = None
         self._decoded = None
@@ -395,15 +397,23 @@ class DictColumn(Column):
 
     # ---- cells -------------------------------------------------------------------------------------
     def valid_at(self, i):
+        if self.indices is None:
+            return self.decoded().valid_at(i)
         return True if self.validity is None else bool((self.validity[i >> 3] >> (i & 7)) & 1)
 
     def value_at(self, i):
+        if self.indices is None:
+            return self.decoded().value_at(i)
         return self.dictionary.value_at(int(self.indices[i]))
 
     def cells_at(self, rows):
+        if self.indices is None:
+            return self.decoded().cells_at(rows)
         return [self.value_at(int(r)) if self.valid_at(int(r)) else None for r in np.asarray(rows, dtype=np.int64)]
 
     def to_pylist(self):
+        if self.indices is None:
+            return self.decoded().cells_at(np.arange(self.length))
         entries = self.dictionary.to_pylist()
         valid = unpack_validity(self.validity, self.length)
         return [entries[i] if v else None for i, v in zip(self.indices.tolist(), valid.tolist())]
@@ -419,17 +429,12 @@ class DictColumn(Column):
         per entry (dq_dict_scan)."""
         import torch
         dev = torch.device("cuda", device) if not isinstance(device, torch.device) else device
-        d, nd = self.dictionary, self.dictionary.length
+        if self.indices is None:
+            raise TypeError("column %s was ingested on the device and has no host buffers to copy" % self.name)
         dd = {"indices": torch.from_numpy(self.indices).to(dev)}
         if self.validity is not None:
             dd["validity"] = torch.from_numpy(pack_validity(unpack_validity(self.validity, self.length))).to(dev)
-        offs = np.asarray(d.offsets, dtype=np.int32)[:nd + 1] if nd else np.zeros(1, np.int32)
-        nbytes = int(offs[-1])
-        dd["dict_values"] = torch.from_numpy(
-            np.concatenate([np.asarray(d.values, dtype=np.uint8)[:nbytes], np.zeros(16, np.uint8)])).to(dev)
-        dd["dict_offsets"] = torch.from_numpy(np.concatenate([offs, offs[-1:]]).astype(np.int32)).to(dev)
-        dvalid = np.concatenate([unpack_validity(d.validity, nd), np.zeros(1, dtype=bool)])
-        dd["dict_validity"] = torch.from_numpy(pack_validity(dvalid)).to(dev)
+        dd.update(_dictionary_device(self.dictionary, dev, torch))
         self.dict_device = dd
         self._decoded = None
         return self
@@ -461,6 +466,20 @@ class DictColumn(Column):
         c.values = self.dict_device["indices"].data_ptr()
         c.validity = self.dict_device["validity"].data_ptr() if self.dict_device.get("validity") is not None else None
         return c
+
+
+def _dictionary_device(d, dev, torch):
+    """The entries of a dictionary (a host STRING column) as the device buffers of DictColumn.dict_device, with the
+    extra NULL entry n_dict."""
+    nd = d.length
+    offs = np.asarray(d.offsets, dtype=np.int32)[:nd + 1] if nd else np.zeros(1, np.int32)
+    nbytes = int(offs[-1])
+    dd = {"dict_values": torch.from_numpy(
+        np.concatenate([np.asarray(d.values, dtype=np.uint8)[:nbytes], np.zeros(16, np.uint8)])).to(dev)}
+    dd["dict_offsets"] = torch.from_numpy(np.concatenate([offs, offs[-1:]]).astype(np.int32)).to(dev)
+    dvalid = np.concatenate([unpack_validity(d.validity, nd), np.zeros(1, dtype=bool)])
+    dd["dict_validity"] = torch.from_numpy(pack_validity(dvalid)).to(dev)
+    return dd
 
 
 def _dict_column_from_arrow(name, arr, pa):
@@ -560,6 +579,17 @@ def _kept_dictionary(t, pa):
     return pa.types.is_dictionary(t) and (pa.types.is_string(t.value_type) or pa.types.is_large_string(t.value_type))
 
 
+def _string_column_from_arrow(name, arr, validity):
+    """A pa.string() array -> a host STRING column over its buffers."""
+    n = len(arr)
+    bufs = arr.buffers()
+    offs = np.frombuffer(bufs[1], dtype=np.int32)[arr.offset:arr.offset + n + 1]
+    data = np.frombuffer(bufs[2], dtype=np.uint8) if bufs[2] is not None else np.zeros(0, np.uint8)
+    base = int(offs[0]) if n else 0
+    end = int(offs[-1]) if n else 0
+    return Column(name, N.TYPE_STRING, data[base:end], validity, (offs - base).astype(np.int32), length=n)
+
+
 def _column_from_arrow(name, arr, pa, wide_decimals=False, dictionaries="decode"):
     t, n = arr.type, len(arr)
     if dictionaries == "keep" and _kept_dictionary(t, pa):
@@ -570,12 +600,7 @@ def _column_from_arrow(name, arr, pa, wide_decimals=False, dictionaries="decode"
     if pa.types.is_large_string(t):
         arr, t = arr.cast(pa.string()), pa.string()
     if pa.types.is_string(t):
-        bufs = arr.buffers()
-        offs = np.frombuffer(bufs[1], dtype=np.int32)[arr.offset:arr.offset + n + 1]
-        data = np.frombuffer(bufs[2], dtype=np.uint8) if bufs[2] is not None else np.zeros(0, np.uint8)
-        base = int(offs[0]) if n else 0
-        end = int(offs[-1]) if n else 0
-        return Column(name, N.TYPE_STRING, data[base:end], validity, (offs - base).astype(np.int32), length=n)
+        return _string_column_from_arrow(name, arr, validity)
     if pa.types.is_boolean(t):
         bits = np.frombuffer(arr.buffers()[1], dtype=np.uint8)
         vals = np.unpackbits(bits, bitorder="little", count=arr.offset + n)[arr.offset:].astype(np.uint8)
@@ -726,7 +751,7 @@ class Table:
         return cls(cols)
 
     @classmethod
-    def from_arrow(cls, table, wide_decimals=False, dictionaries="decode"):
+    def from_arrow(cls, table, wide_decimals=False, dictionaries="decode", device=None, chunk_rows=None):
         """pyarrow.Table (a Spark DataFrame collected through Arrow, or a parquet read) -> Table.
         Fixed-width values and UTF-8 offsets/data are taken from the Arrow buffers without a
         per-row pass; validity bitmaps are realigned to bit 0 and padded; booleans are widened to one
@@ -737,7 +762,15 @@ class Table:
         `dictionaries`: "decode" (default) rebuilds every row of a dictionary-encoded column on the host; "keep" holds
         dictionary<string> columns encoded (DictColumn: int32 indices + the dictionary; chunks with different
         dictionaries are unified), which device-resident tables scan and group without decoding. Dictionaries of
-        other value types decode either way."""
+        other value types decode either way.
+        `device=d`: the Arrow buffers are uploaded as they are and brought into the column layout on GPU d
+        (`_from_arrow_device`, ingest.hip): a device-resident Table equal to `from_arrow(table).to_device(d)`, or that
+        path's error, without a host pass over the rows. With `chunk_rows=k` a table of more than k rows comes back
+        as a ChunkedTable of device tables of k rows, which is how a string column of 2^31 bytes and more loads."""
+        if device is not None:
+            return _from_arrow_device(cls, table, wide_decimals, dictionaries, device, chunk_rows)
+        if chunk_rows is not None:
+            raise ValueError("chunk_rows cuts a device-resident table into chunks: it needs device=")
         import pyarrow as pa
         if dictionaries not in ("decode", "keep"):
             raise ValueError("dictionaries must be 'decode' or 'keep', not %r" % (dictionaries,))
@@ -752,20 +785,23 @@ class Table:
         return cls(cols)
 
     @classmethod
-    def from_parquet(cls, path, columns=None, wide_decimals=False, dictionaries="decode"):
+    def from_parquet(cls, path, columns=None, wide_decimals=False, dictionaries="decode", device=None, chunk_rows=None):
         """Parquet file or directory -> Table (through pyarrow, then `from_arrow`). dictionaries="keep" reads the
-        string columns dictionary-encoded (`read_dictionary`) and holds them so."""
+        string columns dictionary-encoded (`read_dictionary`) and holds them so. `device` and `chunk_rows` are
+        `from_arrow`'s: pyarrow reads the file as before, the table it gives is ingested on the device."""
         import pyarrow as pa
         import pyarrow.parquet as pq
+        if device is None and chunk_rows is not None:
+            raise ValueError("chunk_rows cuts a device-resident table into chunks: it needs device=")
         if dictionaries == "keep":
             schema = pq.ParquetDataset(path).schema
             strings = [f.name for f in schema if (pa.types.is_string(f.type) or pa.types.is_large_string(f.type) or
                                                   _kept_dictionary(f.type, pa)) and
                        (columns is None or f.name in columns)]
             return cls.from_arrow(pq.read_table(path, columns=columns, read_dictionary=strings),
-                                  wide_decimals=wide_decimals, dictionaries="keep")
+                                  wide_decimals=wide_decimals, dictionaries="keep", device=device, chunk_rows=chunk_rows)
         return cls.from_arrow(pq.read_table(path, columns=columns), wide_decimals=wide_decimals,
-                              dictionaries=dictionaries)
+                              dictionaries=dictionaries, device=device, chunk_rows=chunk_rows)
 
     # ---- schema / access ------------------------------------------------------------------------
     @property
@@ -1057,6 +1093,266 @@ def _from_csv_device(cls, path, header, infer_schema, device):
     finally:
         ctx.csv_free(handle)
     return cls(cols)
+
+
+def _arrow_pieces(chunk_lengths, chunk_offsets, chunk_rows=None):
+    """The row ranges of a chunked Arrow column for every output chunk: a list (one entry per output chunk, over rows
+    [0, k), [k, 2k), ... with k = chunk_rows; one chunk of every row without it or when the rows fit one) of lists of
+    pieces (arrow chunk, first row, rows, first output row). `first row` counts in the chunk's BUFFERS, so it includes
+    the chunk's Arrow offset; `first output row` counts inside the output chunk. Pieces are never empty: chunks of
+    zero rows give none, and a column without rows gives one output chunk without pieces. Pure arithmetic: no
+    pyarrow, no torch."""
+    lengths = [int(x) for x in chunk_lengths]
+    total = sum(lengths)
+    if chunk_rows is not None and int(chunk_rows) < 1:
+        raise ValueError("chunk_rows must be at least 1, not %r" % (chunk_rows,))
+    step = total if chunk_rows is None or total <= int(chunk_rows) else int(chunk_rows)
+    out, c, used = [], 0, 0  # the Arrow chunk being handed out and its rows already taken
+    for r0 in range(0, total, step or 1):
+        rows = min(step, total - r0)
+        pieces, at = [], 0
+        while at < rows:
+            if used == lengths[c]:
+                c, used = c + 1, 0
+                continue
+            take = min(lengths[c] - used, rows - at)
+            pieces.append((c, int(chunk_offsets[c]) + used, take, at))
+            used += take
+            at += take
+        out.append(pieces)
+    return out or [[]]
+
+
+class _ArrowUpload:
+    """Byte ranges of Arrow buffers into HBM for `_from_arrow_device`: each range is a zero-copy view of the Arrow
+    buffer (np.frombuffer, then torch), copied once, either into its place in a final buffer (`put`) or into a
+    staging tensor a kernel reads (`stage`, `stage_bits`). The copies run on torch's current stream; the native
+    wrappers wait for that stream before they launch (Context._after_torch_stream) and return after their kernels
+    have finished, so a staging tensor may be dropped as soon as its call returns."""
+
+    def __init__(self, ctx, dev, torch):
+        self.ctx, self.dev, self.torch = ctx, dev, torch
+
+    def view(self, buf, start, stop):
+        import warnings
+        a = np.frombuffer(buf, dtype=np.uint8)[start:stop]
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")  # torch warns that the (read-only) Arrow memory is not writable: it is only read
+            return self.torch.from_numpy(a)
+
+    def empty(self, nbytes):
+        return self.torch.empty(nbytes, dtype=self.torch.uint8, device=self.dev)
+
+    def put(self, dst, at, buf, start, stop):
+        if stop > start:
+            dst[at:at + stop - start].copy_(self.view(buf, start, stop))
+
+    def stage(self, buf, start, stop):
+        return self.view(buf, start, stop).to(self.dev)
+
+    def stage_bits(self, items):
+        """[(bitmap buffer or None, first bit, rows)] -> (the staging tensor, [(ptr or None, bytes, bit0, rows)] as
+        Context.ingest_bits takes them): the bytes first // 8 .. (first + rows + 7) // 8 of each bitmap, each at an
+        8-byte boundary of one tensor."""
+        spans = [(first >> 3, (first + rows + 7) >> 3) if buf is not None else (0, 0) for buf, first, rows in items]
+        stage = self.empty(sum((b - a + 7) & ~7 for a, b in spans))
+        pieces, at = [], 0
+        for (buf, first, rows), (a, b) in zip(items, spans):
+            if buf is None:
+                pieces.append((None, 0, 0, rows))
+                continue
+            self.put(stage, at, buf, a, b)
+            pieces.append((stage.data_ptr() + at, b - a, first & 7, rows))
+            at += (b - a + 7) & ~7
+        return stage, pieces
+
+
+def _piece_nulls(arr, first, rows):
+    """The NULLs of rows [first, first + rows) of an Arrow array's buffers (Arrow's own count over the bitmap)."""
+    if arr.null_count == 0:
+        return 0
+    return arr.null_count if rows == len(arr) else arr.slice(first - arr.offset, rows).null_count
+
+
+def _arrow_device_plain(up, pa, name, t, chunks, pieces, wide_decimals):
+    """The rows `pieces` name (see _arrow_pieces) of the Arrow arrays `chunks`, all of type `t` (not a dictionary), as
+    one device-only Column laid out as `Table.to_device` lays it out. The type decisions and their errors are
+    `_column_from_arrow`'s."""
+    torch, ctx = up.torch, up.ctx
+    n = sum(p[2] for p in pieces)
+    large = pa.types.is_large_string(t)
+    convert, width, prec, scale = None, 0, 0, 0  # convert: (dq_ingest_kind, param) when the cells need a kernel
+    if large or pa.types.is_string(t):
+        spark = N.TYPE_STRING
+    elif pa.types.is_boolean(t):
+        spark = N.TYPE_BOOLEAN
+    elif pa.types.is_decimal(t):
+        if t.precision > 18 and wide_decimals and pa.types.is_decimal128(t):
+            spark, width, convert = N.TYPE_DECIMAL128, 16, (N.INGEST_DECIMAL_WIDE, 0)
+        elif t.precision > 18:
+            raise ValueError("column %s: DecimalType(%d,%d) exceeds the 64-bit unscaled range (wide_decimals=True "
+                             "loads it as a 128-bit decimal column)" % (name, t.precision, t.scale))
+        elif not pa.types.is_decimal128(t):
+            raise ValueError("column %s: Arrow type %s: the device path reads decimal128 cells only" % (name, t))
+        else:
+            spark, width, convert = N.TYPE_DECIMAL, 16, (N.INGEST_DECIMAL_LOW, 0)
+        prec, scale = t.precision, t.scale
+    elif pa.types.is_timestamp(t):
+        spark, width = N.TYPE_TIMESTAMP, 8
+        convert = {"s": (N.INGEST_TIME_MUL, 10 ** 6), "ms": (N.INGEST_TIME_MUL, 1000), "us": None,
+                   "ns": (N.INGEST_TIME_DIV, 1000)}[t.unit]
+    else:
+        spark = {pa.int8(): N.TYPE_BYTE, pa.int16(): N.TYPE_SHORT, pa.int32(): N.TYPE_INT, pa.int64(): N.TYPE_LONG,
+                 pa.float32(): N.TYPE_FLOAT, pa.float64(): N.TYPE_DOUBLE, pa.date32(): N.TYPE_DATE}.get(t)
+        if spark is None:
+            raise ValueError("column %s: Arrow type %s has no Spark counterpart here" % (name, t))
+        width = np.dtype(NUMPY_OF[spark]).itemsize
+    bufs = {c: chunks[c].buffers() for c, _, _, _ in pieces}
+    d = {}
+    # validity: absent when no piece holds a NULL, else the pieces' bitmaps concatenated bitwise in one launch
+    nulls = [_piece_nulls(chunks[c], first, rows) for c, first, rows, _ in pieces]
+    vstage, vpieces = None, [(None, 0, 0, rows) for _, _, rows, _ in pieces]
+    if sum(nulls):
+        vstage, vpieces = up.stage_bits([(bufs[c][0] if k else None, first, rows)
+                                         for (c, first, rows, _), k in zip(pieces, nulls)])
+        d["validity"] = up.empty(max((n + 63) // 64, 1) * 8)
+        ctx.ingest_bits(vpieces, n, False, d["validity"].data_ptr())
+    if spark == N.TYPE_STRING:
+        w, odt = (8, np.int64) if large else (4, np.int32)
+        spans = []
+        for c, first, rows, _ in pieces:  # the two offsets that bound the piece's bytes
+            o = np.frombuffer(bufs[c][1], dtype=odt)
+            spans.append((int(o[first]), int(o[first + rows])))
+        total = sum(b - a for a, b in spans)
+        too_long = ValueError("column %s: its strings hold %d bytes, more than the int32 offsets of one column address "
+                              "(2^31 - 17); chunk_rows=k loads the table as chunks of k rows" % (name, total))
+        if total > 2 ** 31 - 17:
+            raise too_long
+        d["values"] = up.empty(total + 16)
+        d["values"][total:] = 0  # the read-past padding of the dword loads
+        if n == 0:
+            # no piece writes the one offset: the host path leaves the raw Arrow offset of a single empty string chunk
+            # there (nothing reads it), and so does this one
+            first = 0 if len(chunks) != 1 or large else int(np.frombuffer(chunks[0].buffers()[1], dtype=odt)[chunks[0].offset])
+            d["offsets"] = torch.full((1,), first, dtype=torch.int32, device=up.dev)
+        else:
+            d["offsets"] = torch.empty(n + 1, dtype=torch.int32, device=up.dev)
+        base = 0
+        for i, ((c, first, rows, row0), (a, b)) in enumerate(zip(pieces, spans)):
+            up.put(d["values"], base, bufs[c][2], a, b)
+            src = up.stage(bufs[c][1], first * w, (first + rows + 1) * w)
+            if ctx.ingest_offsets(src.data_ptr(), src.numel(), w, rows, base, i == len(pieces) - 1,
+                                  d["offsets"].data_ptr() + 4 * row0):
+                raise too_long
+            base += b - a
+    elif spark == N.TYPE_BOOLEAN:
+        d["values"] = up.empty(n)
+        if n:
+            bits, bpieces = up.stage_bits([(bufs[c][1], first, rows) for c, first, rows, _ in pieces])
+            ctx.ingest_bits(bpieces, n, True, d["values"].data_ptr())
+    else:
+        out_width = np.dtype(NUMPY_OF[spark]).itemsize
+        d["values"] = up.empty(n * out_width)
+        for (c, first, rows, row0), v in zip(pieces, vpieces):
+            if convert is None or (convert[0] == N.INGEST_DECIMAL_WIDE and v[0] is None):
+                up.put(d["values"], row0 * out_width, bufs[c][1], first * width, (first + rows) * width)
+                continue
+            src = up.stage(bufs[c][1], first * width, (first + rows) * width)
+            ctx.ingest_convert(convert[0], src.data_ptr(), src.numel(), v[:3] if v[0] is not None else None, rows,
+                               convert[1], d["values"].data_ptr() + row0 * out_width)
+    del vstage  # vpieces point into it: it had to live until the conversions had read their validity bits
+    col = Column(name, spark, None, None, decimal_precision=prec, decimal_scale=scale, length=n)
+    col.device = d
+    if spark == N.TYPE_TIMESTAMP:
+        col.tz = t.tz
+    return col
+
+
+def _arrow_device_dict(up, pa, name, chunked):
+    """A dictionary<string> ChunkedArray under dictionaries="keep" as a device-only DictColumn: what
+    `_dict_column_from_arrow` and `DictColumn.to_device` build. The dictionary's entries are read on the host (they
+    are few); the indices are widened, checked and folded with the NULL entries on the device."""
+    torch, ctx = up.torch, up.ctx
+    if chunked.num_chunks > 1:
+        chunked = chunked.unify_dictionaries()
+    chunks, t = chunked.chunks, chunked.type
+    entries = chunks[0].dictionary if chunks else pa.array([], type=t.value_type)
+    if pa.types.is_large_string(entries.type):
+        entries = entries.cast(pa.string())
+    dictionary = _string_column_from_arrow(name, entries, _arrow_validity(entries, len(entries)))
+    nd = dictionary.length
+    dd = _dictionary_device(dictionary, up.dev, torch)
+    dict_validity = dd["dict_validity"].data_ptr() if dictionary.validity is not None else None
+    pieces = _arrow_pieces([len(c) for c in chunks], [c.offset for c in chunks])[0]
+    n = sum(p[2] for p in pieces)
+    w, signed = t.index_type.bit_width // 8, pa.types.is_signed_integer(t.index_type)
+    dd["indices"] = torch.empty(n, dtype=torch.int32, device=up.dev)
+    folds, folded, null_rows = [], [], 0  # the pieces' folded bitmaps (kept until they are concatenated)
+    for c, first, rows, row0 in pieces:
+        bufs = chunks[c].buffers()  # of a DictionaryArray: the validity bitmap and the indices
+        v, vstage = None, None  # vstage holds the bytes v points at until the piece's call has returned
+        if _piece_nulls(chunks[c], first, rows):
+            vstage, vp = up.stage_bits([(bufs[0], first, rows)])
+            v = vp[0][:3]
+        fold = up.empty((rows + 63) // 64 * 8) if v is not None or dict_validity else None
+        src = up.stage(bufs[1], first * w, (first + rows) * w)
+        bad_row, bad_index, nulls = ctx.ingest_indices(src.data_ptr(), src.numel(), w, signed, v, rows, nd, dict_validity,
+                                                       dd["indices"].data_ptr() + 4 * row0,
+                                                       fold.data_ptr() if fold is not None else None)
+        if bad_row >= 0:
+            raise ValueError("column %s: row %d has dictionary index %d outside [0, %d)"
+                             % (name, row0 + bad_row, bad_index, nd))
+        null_rows += nulls
+        folds.append(fold)
+        folded.append((fold.data_ptr(), fold.numel(), 0, rows) if fold is not None else (None, 0, 0, rows))
+    if null_rows:
+        dd["validity"] = up.empty(max((n + 63) // 64, 1) * 8)
+        ctx.ingest_bits(folded, n, False, dd["validity"].data_ptr())
+    del folds  # `folded` pointed into them
+    col = DictColumn(name, None, None, dictionary, length=n)
+    col.dict_device = dd
+    return col
+
+
+def _from_arrow_device(cls, table, wide_decimals, dictionaries, device, chunk_rows):
+    """Table.from_arrow on the GPU (ingest.hip). The host reads metadata only: per column and Arrow chunk the type,
+    offset, length, null count, buffer addresses and the two string offsets that bound a piece; it never walks the
+    rows (no combine_chunks, cast, unpackbits or copy of a row buffer). Two exceptions pyarrow already implements stay
+    on the host: dictionary_decode() of a dictionary column that is not kept, and unify_dictionaries() of a kept one
+    whose chunks carry different dictionaries. Columns are taken in order, so the first error is the host path's."""
+    import pyarrow as pa
+    import torch
+    from . import engine
+    if dictionaries not in ("decode", "keep"):
+        raise ValueError("dictionaries must be 'decode' or 'keep', not %r" % (dictionaries,))
+    if chunk_rows is not None and int(chunk_rows) < 1:
+        raise ValueError("chunk_rows must be at least 1, not %r" % (chunk_rows,))
+    dev = device if isinstance(device, torch.device) else torch.device("cuda", int(device))
+    ctx = engine.ctx()
+    if ctx.multi or ctx.device != dev.index:
+        ctx = N.context(dev.index)
+    up = _ArrowUpload(ctx, dev, torch)
+    n = table.num_rows
+    chunked_out = chunk_rows is not None and n > int(chunk_rows)
+    step = int(chunk_rows) if chunked_out else None
+    out = [[] for _ in range((n + step - 1) // step if chunked_out else 1)]
+    for name, column in zip(table.column_names, table.columns):
+        t = column.type
+        if dictionaries == "keep" and _kept_dictionary(t, pa):
+            # a chunk's dictionary is that of its own rows, as from_arrow(table.slice(...)) has it
+            cols = [_arrow_device_dict(up, pa, name, column.slice(k * step, step) if chunked_out else column)
+                    for k in range(len(out))]
+        else:
+            chunks = column.chunks
+            if pa.types.is_dictionary(t):
+                chunks, t = [c.dictionary_decode() for c in chunks], t.value_type
+            plan = _arrow_pieces([len(c) for c in chunks], [c.offset for c in chunks], step)
+            cols = [_arrow_device_plain(up, pa, name, t, chunks, pieces, wide_decimals) for pieces in plan]
+        for tcols, col in zip(out, cols):
+            tcols.append(col)
+    torch.cuda.current_stream(dev).synchronize()  # the uploads ran on torch's stream, the scans run on the context's
+    tables = [cls(cols) for cols in out]
+    return ChunkedTable(tables) if chunked_out else tables[0]
 
 
 def _concat_host(parts):

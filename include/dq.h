@@ -335,7 +335,12 @@ typedef enum dq_scan_kernel {
     DQ_KERNEL_CSV_ROWS = 20,      /* csv_rows_kernel: record starts                                                */
     DQ_KERNEL_CSV_FIELDS = 21,    /* csv_fields_kernel: field spans, classes and ambiguity reports                 */
     DQ_KERNEL_CSV_COLUMN = 22,    /* the per-column kernels of dq_csv_column (lengths, gather, typed parse)        */
-    DQ_KERNEL_COUNT = 23
+    DQ_KERNEL_INGEST_VALIDITY = 23, /* ingest_validity_kernel: validity bitmaps of Arrow chunks concatenated bitwise  */
+    DQ_KERNEL_INGEST_BOOL = 24,   /* ingest_bool_kernel: Arrow boolean bits into one byte per row                  */
+    DQ_KERNEL_INGEST_OFFSETS = 25, /* ingest_offsets_kernel: string offsets of one Arrow chunk rebased into int32   */
+    DQ_KERNEL_INGEST_CONVERT = 26, /* the typed conversions of dq_ingest_convert (decimal cells, timestamp units)   */
+    DQ_KERNEL_INGEST_INDICES = 27, /* ingest_indices_kernel: dictionary indices widened, checked and folded         */
+    DQ_KERNEL_COUNT = 28
 } dq_scan_kernel;
 int64_t dq_scan_kernel_launches(const dq_ctx* ctx, int32_t kernel);
 
@@ -783,6 +788,62 @@ int dq_csv_field(dq_ctx* ctx, const dq_csv* csv, int64_t row, int32_t col, int64
 int dq_csv_column(dq_ctx* ctx, const dq_csv* csv, int32_t col, int32_t spark_type, void* out_values, uint8_t* out_validity,
                   int32_t* out_offsets, int64_t* out_bytes);
 void dq_csv_free(dq_ctx* ctx, dq_csv* csv);
+
+/* ---- Arrow buffers brought into the engine's layout on the device (Table.from_arrow(t, device=...)) ------------------
+ * The caller uploads byte ranges of Arrow buffers as they are; these calls do the per-row work that remains. Every
+ * pointer but `pieces` and the reports is device memory. A source is read inside [src, src + src_bytes) only: bytes
+ * at and past src_bytes count as zero and are never loaded. No kernel uses an atomic on an output word, and no result
+ * depends on the launch grid. Every call returns after its kernels have finished (a staging buffer may be released
+ * when it returns). Single-device contexts only (DQ_ERR_UNSUPPORTED otherwise); DQ_ERR_ALIGNMENT for a source or
+ * output that is not aligned as stated. */
+typedef struct dq_ingest_piece {
+    const uint8_t* src; /* LSB-first bits, 8-B aligned; NULL (validity only): the piece has no bitmap, every row is valid */
+    int64_t src_bytes;  /* bytes uploaded at src */
+    int64_t src_bit0;   /* the bit of the piece's first row (the Arrow offset modulo 8 when src starts at byte offset/8) */
+    int64_t rows;       /* > 0 */
+    int64_t out_row0;   /* the piece's first output row: 0 for the first piece, then the rows before it */
+} dq_ingest_piece;
+/* Bits of consecutive pieces (host array; they cover rows [0, nrows) in order) as one output, one launch:
+ *   to_bytes == 0: the validity bitmap, (nrows + 63) / 64 words at `out` (8-B aligned), every word written, bits at
+ *     and past nrows 0. A lane owns whole output words and assembles each from the source words of the pieces that
+ *     cover its 64 rows, so pieces that meet inside a word need no atomics. DQ_KERNEL_INGEST_VALIDITY.
+ *   to_bytes != 0: one byte (0 / 1) per row, nrows bytes at `out` (8-B aligned); src must not be NULL.
+ *     DQ_KERNEL_INGEST_BOOL.
+ * nrows == 0 launches nothing. DQ_ERR_INVALID_ARGUMENT for pieces that are empty, out of order, do not cover the rows
+ * or whose source is shorter than their bits. */
+int dq_ingest_bits(dq_ctx* ctx, const dq_ingest_piece* pieces, int32_t npieces, int64_t nrows, int32_t to_bytes,
+                   void* out);
+/* String offsets of one piece: out[i] = src[i] - src[0] + base for 0 <= i < rows, and for i == rows when write_last
+ * (the column's last piece). src holds rows + 1 offsets of src_width 4 (int32) or 8 (int64: Arrow large_string) bytes,
+ * aligned to their width; out is 4-B aligned. *out_of_range (host) = 1 when a written value lies outside [0, 2^31),
+ * else 0; the values are then undefined. One launch, DQ_KERNEL_INGEST_OFFSETS. */
+int dq_ingest_offsets(dq_ctx* ctx, const void* src, int64_t src_bytes, int32_t src_width, int64_t rows, int64_t base,
+                      int32_t write_last, int32_t* out, int32_t* out_of_range);
+typedef enum dq_ingest_kind {
+    DQ_INGEST_DECIMAL_LOW = 1, /* 16-byte decimal128 cell -> its low 8 bytes (precision <= 18); a NULL cell -> 0 */
+    DQ_INGEST_DECIMAL_WIDE = 2, /* 16-byte cell -> the same cell; a NULL cell -> 0                                */
+    DQ_INGEST_TIME_MUL = 3,    /* int64 * param, wrapping modulo 2^64 (s, ms -> us)                               */
+    DQ_INGEST_TIME_DIV = 4     /* int64 / param, truncated toward zero (ns -> us); param > 0                      */
+} dq_ingest_kind;
+/* One piece of fixed-width cells converted into its place in the final buffer: `rows` cells at src (16-B aligned for
+ * the decimal kinds, else 8-B) to `out` (aligned to its cell). `validity` (8-B aligned, validity_bytes uploaded, the
+ * first row at bit validity_bit0; NULL: no NULLs) is read by the decimal kinds only. One launch,
+ * DQ_KERNEL_INGEST_CONVERT; rows == 0 launches nothing. */
+int dq_ingest_convert(dq_ctx* ctx, int32_t kind, const void* src, int64_t src_bytes, const uint8_t* validity,
+                      int64_t validity_bytes, int64_t validity_bit0, int64_t rows, int64_t param, void* out);
+typedef struct dq_ingest_index_report {
+    int64_t bad_row;   /* the smallest row of the piece whose index lies outside [0, n_dict) although it is valid; -1: none */
+    int64_t bad_index; /* that row's index */
+    int64_t null_rows; /* rows that are NULL after the fold (undefined when bad_row >= 0) */
+} dq_ingest_index_report;
+/* Dictionary indices of one piece (index_width 1 / 2 / 4 / 8 bytes, index_signed or not, aligned to 8 B at src)
+ * -> int32 at out (4-B aligned). A row is NULL when its bit in `validity` (as in dq_ingest_convert) is clear or its
+ * entry's bit in dict_validity (n_dict bits, NULL: no NULL entries) is clear; a NULL row's index is 0. The NULL rows go
+ * to out_validity (8-B aligned, (rows + 63) / 64 words, the piece's first row at bit 0, bits past the rows 0; may be
+ * NULL). An index outside [0, n_dict) counts on a valid row only (report). One launch, DQ_KERNEL_INGEST_INDICES. */
+int dq_ingest_indices(dq_ctx* ctx, const void* src, int64_t src_bytes, int32_t index_width, int32_t index_signed,
+                      const uint8_t* validity, int64_t validity_bytes, int64_t validity_bit0, int64_t rows, int64_t n_dict,
+                      const uint8_t* dict_validity, int32_t* out, uint8_t* out_validity, dq_ingest_index_report* report);
 
 /* Train / test row split (ConstraintSuggestionRunner.useTrainTestSplitWithTestsetRatio). Row r of this call is global
  * row g = row0 + r. h = XXH64 of the 8 little-endian bytes of g with seed `seed`: Spark's XXH64.hashLong(g, seed), the
