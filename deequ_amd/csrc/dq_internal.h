@@ -398,6 +398,8 @@ struct dq_ctx {
     int64_t scan_launches = 0;
     int64_t kernel_launches[DQ_KERNEL_COUNT] = {};  // by dq_scan_kernel
     int64_t freq_paths[DQ_FREQ_PATH_COUNT] = {};     // by dq_freq_path
+    int64_t csv_write_launches[DQ_CSV_WRITE_KERNEL_COUNT] = {};  // by dq_csv_write_kernel (csv_write.hip)
+    int64_t csv_write_routes[DQ_CSV_WRITE_ROUTE_COUNT] = {};     // by dq_csv_write_route
     int64_t schema_launches = 0;                     // schema_verdict_kernel launches (dq_schema_launch_count)
     // Released device scratch of the grouping builds (multi-GB partition buffers and tables), re-used in stream
     // order instead of a hipMalloc / hipFree pair per call; bounded, freed at dq_close and on allocation failure.

@@ -71,6 +71,11 @@ SCAN_KERNELS = ("striped", "striped_heavy", "heavy8", "heavy8_full", "bits", "pr
                 "filter_validity", "row_outcomes", "freq_probe")
 # the dq_scan_kernel entries after them: the kernels of the device CSV reader (dq_csv_index, dq_csv_column)
 CSV_KERNELS = ("csv_quotes", "csv_mark", "csv_rows", "csv_fields", "csv_column")
+# the device CSV writer counts on its own (dq_csv_write_launch_count, dq_csv_write_route_count), in enum order
+CSV_WRITE_KERNELS = ("csv_write_mark", "csv_write_sizes", "csv_write_write")
+CSV_WRITE_ROUTES = ("stage", "direct")
+CSV_WRITE_STAGE_BYTES = 31744  # dq.h DQ_CSV_WRITE_STAGE_BYTES
+CSV_WRITE_TILE_ROWS = 256      # rows of one tile of the write kernel
 # and after those: the kernels that bring uploaded Arrow buffers into the column layout (dq_ingest_*)
 INGEST_KERNELS = ("ingest_validity", "ingest_bool", "ingest_offsets", "ingest_convert", "ingest_indices")
 # dq_ingest_kind
@@ -90,6 +95,7 @@ EXPORTED_SYMBOLS = (
     "dq_parse_timestamp", "dq_split_rows", "dq_split_row_is_test", "dq_dec128_to_double",
     "dq_dict_scan", "dq_dict_counts", "dq_dict_decode", "dq_filter_validity", "dq_freq_row_bits", "dq_row_outcomes",
     "dq_freq_probe", "dq_csv_index", "dq_csv_field", "dq_csv_column", "dq_csv_free",
+    "dq_csv_write_size", "dq_csv_write", "dq_csv_write_launch_count", "dq_csv_write_route_count",
     "dq_ingest_bits", "dq_ingest_offsets", "dq_ingest_convert", "dq_ingest_indices",
 )
 
@@ -395,6 +401,10 @@ def load_library(path=None):
             "dq_csv_column": (c_int, [c_void_p, c_void_p, ctypes.c_int32, ctypes.c_int32, c_void_p, c_void_p, c_void_p,
                                       c_void_p]),
             "dq_csv_free": (None, [c_void_p, c_void_p]),
+            "dq_csv_write_size": (c_int, [c_void_p, c_void_p, ctypes.c_int32, c_int64, c_void_p, c_void_p]),
+            "dq_csv_write": (c_int, [c_void_p, c_void_p, ctypes.c_int32, c_int64, c_void_p, c_void_p, c_int64]),
+            "dq_csv_write_launch_count": (c_int64, [c_void_p, ctypes.c_int32]),
+            "dq_csv_write_route_count": (c_int64, [c_void_p, ctypes.c_int32]),
             "dq_ingest_bits": (c_int, [c_void_p, c_void_p, ctypes.c_int32, c_int64, ctypes.c_int32, c_void_p]),
             "dq_ingest_offsets": (c_int, [c_void_p, c_void_p, c_int64, ctypes.c_int32, c_int64, c_int64, ctypes.c_int32,
                                           c_void_p, c_void_p]),
@@ -829,6 +839,44 @@ class Context:
     def csv_free(self, handle):
         if handle:
             self.lib.dq_csv_free(self.handle, ctypes.c_void_p(handle))
+
+    def csv_write_kernel_launches(self):
+        """{kernel name: launches so far} of the device CSV writer (dq_csv_write_launch_count)."""
+        return {name: int(self.lib.dq_csv_write_launch_count(self.handle, i)) for i, name in enumerate(CSV_WRITE_KERNELS)}
+
+    def csv_write_routes(self):
+        """{route: tiles of the write kernel that took it so far} (dq_csv_write_route_count)."""
+        return {name: int(self.lib.dq_csv_write_route_count(self.handle, i)) for i, name in enumerate(CSV_WRITE_ROUTES)}
+
+    def csv_write_size(self, columns, nrows, row_start_ptr):
+        """dq_csv_write_size: fills row_start (device, nrows + 1 int64); returns the body's bytes."""
+        self._after_torch_stream()
+        col_arr = (DqColumn * max(len(columns), 1))(*columns)
+        total = ctypes.c_int64(0)
+        self.check(self.lib.dq_csv_write_size(self.handle, col_arr, len(columns), int(nrows),
+                                              ctypes.c_void_p(row_start_ptr), ctypes.byref(total)), "dq_csv_write_size")
+        return int(total.value)
+
+    def csv_write_body(self, columns, nrows, row_start_ptr, out_ptr, out_bytes):
+        """dq_csv_write: the body into out (device, out_bytes bytes) from the sizing call's row_start."""
+        self._after_torch_stream()
+        col_arr = (DqColumn * max(len(columns), 1))(*columns)
+        self.check(self.lib.dq_csv_write(self.handle, col_arr, len(columns), int(nrows), ctypes.c_void_p(row_start_ptr),
+                                         ctypes.c_void_p(out_ptr) if out_ptr else None, int(out_bytes)), "dq_csv_write")
+
+    def csv_write(self, columns, nrows, device, limit=2 ** 31):
+        """The CSV body of device columns (a list of DqColumn) as a device uint8 tensor, without touching disk: the
+        sizing call, one allocation, the write call. A body of `limit` bytes or more raises ValueError."""
+        import torch
+        dev = device if isinstance(device, torch.device) else torch.device("cuda", int(device))
+        row_start = torch.empty(int(nrows) + 1, dtype=torch.int64, device=dev)
+        total = self.csv_write_size(columns, nrows, row_start.data_ptr())
+        if total >= limit:
+            raise ValueError("the CSV body holds %d bytes: the device writer takes bodies below 2^31 bytes; a "
+                             "ChunkedTable writes its chunks one after the other" % total)
+        out = torch.empty(total, dtype=torch.uint8, device=dev)
+        self.csv_write_body(columns, nrows, row_start.data_ptr(), out.data_ptr() if total else None, total)
+        return out
 
     def ingest_kernel_launches(self):
         """{kernel name: launches so far} of the Arrow ingest (the DQ_KERNEL_INGEST_* entries)."""

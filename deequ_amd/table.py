@@ -673,6 +673,186 @@ def column_to_arrow(col, pa):
     return pa.array(np.asarray(col.values, dtype=NUMPY_OF[t])[:n], mask=mask)
 
 
+# ---- CSV output: the host path (the definition of Table.to_csv) -----------------------------------------
+def _java_float_text(x, is_float):
+    """Double.toString / Float.toString: the shortest digits that round-trip, plain for 1e-3 <= |x| < 1e7."""
+    x = np.float32(x) if is_float else float(x)
+    if x != x:
+        return "NaN"
+    if math.isinf(x):
+        return "Infinity" if x > 0 else "-Infinity"
+    if x == 0:
+        return "-0.0" if math.copysign(1.0, x) < 0 else "0.0"
+    mant, exp = np.format_float_scientific(x, unique=True, trim="0").split("e")  # d.ddd, at least one fraction digit
+    sign, mant = ("-", mant[1:]) if mant[0] == "-" else ("", mant)
+    e = int(exp)
+    if not (np.float32(1e-3) if is_float else 1e-3) <= abs(x) < 1e7:
+        return "%s%sE%d" % (sign, mant, e)
+    digits = mant.replace(".", "")
+    if e < 0:
+        return sign + "0." + "0" * (-e - 1) + (digits.rstrip("0") or "0")
+    digits = digits.ljust(e + 2, "0")
+    return sign + digits[:e + 1] + "." + digits[e + 1:]
+
+
+def _java_civil(days):
+    """(year of era, month, day) of a day number in java.util.GregorianCalendar: Gregorian from 1582-10-15 (Julian Day
+    2299161), Julian before (E. G. Richards' day-number conversion; every // floors)."""
+    j = days + 2440588
+    f = j + 1401
+    if j >= 2299161:
+        f += (4 * j + 274277) // 146097 * 3 // 4 - 38
+    e = 4 * f + 3
+    h = 5 * (e % 1461 // 4) + 2
+    day, month = h % 153 // 5 + 1, (h // 153 + 2) % 12 + 1
+    year = e // 1461 - 4716 + (14 - month) // 12
+    return (year if year >= 1 else 1 - year), month, day
+
+
+def _date_text(days):
+    return "%04d-%02d-%02d" % _java_civil(days)
+
+
+def _timestamp_text(micros):
+    secs, frac = divmod(micros, 1000000)
+    days, sod = divmod(secs, 86400)
+    text = "%s %02d:%02d:%02d" % (_date_text(days), sod // 3600, sod // 60 % 60, sod % 60)
+    return text + (".%06d" % frac).rstrip("0") if frac else text
+
+
+def _decimal_text(unscaled, scale):
+    """BigDecimal.toString of unscaled * 10^-scale (scale >= 0): scientific when the adjusted exponent is below -6."""
+    sign, digits = ("-" if unscaled < 0 else ""), str(abs(unscaled))
+    adjusted = len(digits) - 1 - scale
+    if scale == 0:
+        return sign + digits
+    if adjusted >= -6:
+        digits = digits.rjust(scale + 1, "0")
+        return sign + digits[:-scale] + "." + digits[-scale:]
+    return sign + digits[0] + ("." + digits[1:] if len(digits) > 1 else "") + "E%d" % adjusted
+
+
+def _csv_cell_bytes(col, i):
+    """The bytes of the non-NULL cell i of a host column in a CSV file: Spark 2.2's Cast(x AS STRING); a STRING cell
+    in quotes, every quote doubled, iff it holds ',', '"', LF or CR or is empty."""
+    t = col.spark_type
+    if t == N.TYPE_STRING:
+        return _csv_quoted(bytes(col.values[col.offsets[i]:col.offsets[i + 1]]))
+    v = col.values[i]
+    if t == N.TYPE_BOOLEAN:
+        text = "true" if v else "false"
+    elif t in (N.TYPE_FLOAT, N.TYPE_DOUBLE):
+        text = _java_float_text(v, t == N.TYPE_FLOAT)
+    elif t == N.TYPE_DECIMAL:
+        text = _decimal_text(int(v), col.decimal_scale)
+    elif t == N.TYPE_DATE:
+        text = _date_text(int(v))
+    elif t == N.TYPE_TIMESTAMP:
+        text = _timestamp_text(int(v))
+    else:
+        text = str(int(v))
+    return text.encode("ascii")
+
+
+def _csv_quoted(b):
+    if b == b"" or any(c in b for c in b',"\n\r'):
+        return b'"' + b.replace(b'"', b'""') + b'"'
+    return b
+
+
+def _csv_header(names):
+    return b",".join(_csv_quoted(n.encode("utf-8")) for n in names) + b"\n"
+
+
+def _csv_refuse_wide(table):
+    for c in table.columns.values():
+        if c.spark_type == N.TYPE_DECIMAL128:
+            raise ValueError("column %s: %s has no CSV text yet (a 128-bit BigDecimal.toString is a later step); cast or "
+                             "drop the column" % (c.name, c.type_name))
+
+
+def _csv_body_host(table):
+    cols = [c.decoded() if isinstance(c, DictColumn) else c for c in table.columns.values()]
+    valid = [unpack_validity(c.validity, c.length) for c in cols]
+    return b"".join(b",".join(_csv_cell_bytes(c, i) if v[i] else b"" for c, v in zip(cols, valid)) + b"\n"
+                    for i in range(table.nrows))
+
+
+def _csv_body_device(table):
+    """The CSV body of a device-resident table as a device uint8 tensor (csv_write.hip through Context.csv_write)."""
+    from . import engine
+    cols = list(table.columns.values())
+    missing = [c.name for c in cols if c.device is None]
+    if missing:
+        raise ValueError("to_csv of a device table: column %s has no device buffers (to_device() first)" % missing[0])
+    first = cols[0].device["values"] if cols[0].device.get("values") is not None else cols[0].device["offsets"]
+    dev = first.device
+    ctx = engine.ctx()
+    if not ctx.multi and ctx.device != dev.index:
+        ctx = N.context(dev.index)
+    return ctx.csv_write([c.native() for c in cols], table.nrows, dev)
+
+
+def _is_device_table(table):
+    return any(c.device is not None for c in table.columns.values())
+
+
+def _csv_body(table):
+    """bytes (host table) or a device uint8 tensor (device table)."""
+    _csv_refuse_wide(table)
+    if not table.columns:
+        raise ValueError("to_csv: a table without columns has no records")
+    return _csv_body_device(table) if _is_device_table(table) else _csv_body_host(table)
+
+
+def _csv_write_file(path, names, header, bodies):
+    """The header, then every body (bytes, or a device tensor that is downloaded once), into `path`; the bytes written."""
+    total = 0
+    with open(path, "wb") as f:
+        if header:
+            total += f.write(_csv_header(names))
+        for b in bodies:
+            if not isinstance(b, bytes):
+                b = b.cpu().numpy()
+            total += f.write(b)
+    return total
+
+
+def _column_to_host(c):
+    """A device-resident column as a host column: every buffer downloaded once (the inverse of to_device)."""
+    if isinstance(c, DictColumn):
+        dd = c.dict_device
+        validity = dd["validity"].cpu().numpy() if dd.get("validity") is not None else None
+        return DictColumn(c.name, dd["indices"].cpu().numpy(), validity, c.dictionary)
+    d, n = c.device, c.length
+    validity = d["validity"].reshape(-1).cpu().numpy().view(np.uint8) if d.get("validity") is not None else None
+    if c.spark_type == N.TYPE_STRING:
+        offsets = d["offsets"].cpu().numpy()
+        end = int(offsets[n]) if len(offsets) > n else 0
+        out = Column(c.name, c.spark_type, d["values"][:end].cpu().numpy(), validity, offsets, length=n)
+        if getattr(c, "offsets64", False):
+            out.offsets64 = True
+    else:
+        dt = np.dtype(NUMPY_OF[c.spark_type])
+        raw = d["values"].reshape(-1).cpu().numpy().view(np.uint8)[:n * dt.itemsize]
+        out = Column(c.name, c.spark_type, raw.view(dt), validity, decimal_precision=c.decimal_precision,
+                     decimal_scale=c.decimal_scale, length=n)
+    out.tz = c.tz
+    return out
+
+
+def _table_to_arrow(table):
+    import pyarrow as pa
+    host = table.to_host()
+    arrays = []
+    for c in host.columns.values():
+        a = column_to_arrow(c, pa)
+        if c.spark_type == N.TYPE_TIMESTAMP and c.tz is not None:
+            a = a.cast(pa.timestamp("us", tz=c.tz))
+        arrays.append(a)
+    return pa.Table.from_arrays(arrays, names=list(host.columns))
+
+
 class Table:
     """Named columns of equal length (the DataFrame stand-in of the drop-in API)."""
 
@@ -858,6 +1038,33 @@ class Table:
             c.device = d
         return self
 
+    def to_host(self):
+        """The inverse of `to_device`, buffer for buffer: a new host Table whose values, validity words, int32 offsets,
+        dictionary indices and entries are the device buffers downloaded once each (a column without a bitmap stays
+        without one). A host table returns itself."""
+        if not _is_device_table(self):
+            return self
+        return Table([_column_to_host(c) if c.device is not None else c for c in self.columns.values()])
+
+    def to_arrow(self):
+        """The table as a pyarrow.Table (`column_to_arrow` per column over the buffers; a device table is downloaded
+        once, `to_host`): no per-row Python. `Table.from_arrow(t.to_arrow(), wide_decimals=True, dictionaries="keep")`
+        gives back the buffers of `t`."""
+        return _table_to_arrow(self)
+
+    def to_parquet(self, path):
+        """`pyarrow.parquet.write_table` of `to_arrow()`."""
+        import pyarrow.parquet as pq
+        pq.write_table(self.to_arrow(), path)
+
+    def to_csv(self, path, header=True):
+        """Write the table as CSV: ',' delimiter, '"' quote, doubled-quote escape, LF after every
+        record; a cell is Spark 2.2's Cast(x AS STRING), NULL is zero bytes, a STRING cell is quoted iff it holds ',',
+        '"', LF or CR or is empty. A host table is written by the host path (`_csv_body_host`: the definition), a
+        device-resident table by csv_write.hip, byte for byte the same file. DECIMAL128 columns and device bodies of
+        2^31 bytes and more raise ValueError. Returns the bytes written."""
+        return _csv_write_file(path, self.fieldNames, header, [_csv_body(self)])
+
 
 class ChunkedTable:
     """A table held as consecutive row chunks (Arrow record batches) of one schema: the shape of a DataFrame's
@@ -894,6 +1101,16 @@ class ChunkedTable:
 
     def count(self):
         return self.nrows
+
+    def to_arrow(self):
+        """The chunks' `Table.to_arrow()` tables concatenated."""
+        import pyarrow as pa
+        return pa.concat_tables([t.to_arrow() for t in self.chunks])
+
+    def to_csv(self, path, header=True):
+        """The header once, then every chunk's body appended (`Table.to_csv`): the file of the concatenated table.
+        Each chunk's body is below 2^31 bytes on the device; the file may be larger. Returns the bytes written."""
+        return _csv_write_file(path, self.fieldNames, header, (_csv_body(t) for t in self.chunks))
 
     def concat(self, names):
         """The named columns of every chunk as one Table, concatenated where the chunks live (HBM when every chunk is

@@ -789,6 +789,47 @@ int dq_csv_column(dq_ctx* ctx, const dq_csv* csv, int32_t col, int32_t spark_typ
                   int32_t* out_offsets, int64_t* out_bytes);
 void dq_csv_free(dq_ctx* ctx, dq_csv* csv);
 
+/* ---- CSV bodies written on the device (Table.to_csv of a device-resident table) ------------------------
+ * The dialect is the reader's above. Every record, the last included, ends with LF (never CR LF); cells are separated
+ * by ','. A NULL cell is zero bytes. A non-NULL cell is Spark 2.2's Cast(x AS STRING): BOOLEAN true / false; BYTE,
+ * SHORT, INT, LONG decimal digits; FLOAT / DOUBLE Float.toString / Double.toString (shortest round-trip digits);
+ * DECIMAL (precision <= 18) BigDecimal.toString; DATE yyyy-MM-dd; TIMESTAMP timestampToString in a UTC session zone.
+ * A STRING cell is its bytes as they are (not validated as UTF-8), enclosed in quotes with every '"' doubled if and
+ * only if it holds ',', '"', LF or CR or is the empty string; no other cell is ever quoted. The header is the caller's.
+ *
+ * Every column is a device column (DQ_COL_DEVICE) of nrows rows; DQ_COL_OFFSETS64 is honoured. DQ_TYPE_DECIMAL128 has
+ * no text here: DQ_ERR_UNSUPPORTED naming the column. Single-device contexts only (DQ_ERR_UNSUPPORTED otherwise).
+ * Two calls with the same columns:
+ *   dq_csv_write_size  fills row_start (device, nrows + 1 int64, 8-B aligned) with the byte offset of every record in
+ *                      the body, row_start[nrows] = *out_bytes = the body's size.
+ *   dq_csv_write       writes the body into `out` (device, out_bytes bytes = that size, any alignment) from the same
+ *                      columns and row_start; nothing outside [out, out + out_bytes) is written.
+ * Kernel launches depend on the number and the types of the columns, never on the rows or the bytes: each call
+ * launches DQ_CSV_WRITE_KERNEL_MARK once per STRING column (the C-ABI keeps no state between the calls), the first
+ * DQ_CSV_WRITE_KERNEL_SIZES once, the second DQ_CSV_WRITE_KERNEL_WRITE once (not for nrows == 0). The write kernel
+ * takes tiles of 256 consecutive rows: a tile whose bytes fit DQ_CSV_WRITE_STAGE_BYTES of LDS is assembled there and
+ * flushed with aligned 16-byte stores (DQ_CSV_WRITE_ROUTE_STAGE), any other tile writes to `out` directly
+ * (DQ_CSV_WRITE_ROUTE_DIRECT); the bytes are the same. */
+#define DQ_CSV_WRITE_STAGE_BYTES 31744 /* 31 KiB: five workgroups of the write kernel fit a CU's 160 KiB of LDS */
+typedef enum dq_csv_write_kernel {
+    DQ_CSV_WRITE_KERNEL_MARK = 0,  /* csvw_mark_kernel: the quote bitmaps of one STRING column   */
+    DQ_CSV_WRITE_KERNEL_SIZES = 1, /* csvw_sizes_kernel: the bytes of every record               */
+    DQ_CSV_WRITE_KERNEL_WRITE = 2, /* csvw_write_kernel: the body                                */
+    DQ_CSV_WRITE_KERNEL_COUNT = 3
+} dq_csv_write_kernel;
+typedef enum dq_csv_write_route {
+    DQ_CSV_WRITE_ROUTE_STAGE = 0,  /* tiles assembled in LDS           */
+    DQ_CSV_WRITE_ROUTE_DIRECT = 1, /* tiles written to global memory   */
+    DQ_CSV_WRITE_ROUTE_COUNT = 2
+} dq_csv_write_route;
+int dq_csv_write_size(dq_ctx* ctx, const dq_column* columns, int32_t ncols, int64_t nrows, int64_t* row_start,
+                      int64_t* out_bytes);
+int dq_csv_write(dq_ctx* ctx, const dq_column* columns, int32_t ncols, int64_t nrows, const int64_t* row_start,
+                 uint8_t* out, int64_t out_bytes);
+/* Launches so far of one dq_csv_write_kernel / tiles so far that took one dq_csv_write_route; -1 for a bad index. */
+int64_t dq_csv_write_launch_count(const dq_ctx* ctx, int32_t kernel);
+int64_t dq_csv_write_route_count(const dq_ctx* ctx, int32_t route);
+
 /* ---- Arrow buffers brought into the engine's layout on the device (Table.from_arrow(t, device=...)) ------------------
  * The caller uploads byte ranges of Arrow buffers as they are; these calls do the per-row work that remains. Every
  * pointer but `pieces` and the reports is device memory. A source is read inside [src, src + src_bytes) only: bytes
