@@ -15,12 +15,11 @@
 #include <string.h>
 
 #include <algorithm>
-#include <map>
 #include <string>
 #include <tuple>
 #include <vector>
-#include <vector>
 
+#include "call_plans.h"
 #include "dq_common.h"
 #include "dq_dict.h"
 #include "dq_internal.h"
@@ -167,12 +166,6 @@ struct Stager {
         return DQ_OK;
     }
 };
-
-// Staging bytes of one run_predicate.
-size_t pred_stage_bytes(const dq_predicate& pr) {
-    return align_up(sizeof(PredProgram), 16) + align_up(sizeof(int32_t) * (size_t)pr.code_len, 16) +
-           align_up(sizeof(dq_const) * (size_t)std::max(pr.n_consts, 0), 16) + align_up((size_t)std::max<int64_t>(pr.strings_len, 0), 16);
-}
 
 PredColumn pred_column(const dq_column& col, const void* values, const void* validity, const void* offsets) {
     PredColumn pc;
@@ -643,6 +636,110 @@ int read_back(ScanCall& sc, Stager& up, const dq_state* dout, dq_state* out, uin
     return DQ_OK;
 }
 
+// ---- the predicate-bitmap stage of dq_filter_validity and dq_row_outcomes ---------------------------------------------
+// A validated call whose ops are one dummy Size(where = p) per predicate (size_where_ops) goes through dq_scan's own
+// stages, planned for the bitmap pass (the caller's sc.options.where_masks = false): run_predicates leaves each
+// predicate's TRUE / NOT-NULL bitmaps in the arena, once per predicate, and the scan launch itself is never issued.
+// extra_pinned: staging of what the caller reads back after it. Without predicates nothing is planned or staged (the
+// context's arena is not touched).
+int predicate_bitmaps(ScanCall& sc, Stager& up, size_t extra_pinned) {
+    dq_ctx* ctx = sc.ctx;
+    int rc;
+    if (sc.npreds > 0) {
+        std::string msg;
+        rc = plan_scan(sc.columns, sc.ncols, sc.nrows, sc.ops, sc.nops, sc.preds, sc.npreds, sc.use, sc.options, &sc.plan, &msg);
+        if (rc) return fail(ctx, rc, "%s", msg.c_str());
+        if ((rc = scan_geometry(sc))) return rc;
+        sc.L = layout_scan(sc.plan, sc.geo, sc.use, sc.columns, sc.ncols, sc.nrows, sc.nops, sc.preds, sc.npreds, true);
+        if ((rc = ensure_arena(ctx, sc.L.arena_bytes))) return rc;
+    }
+    if ((rc = ensure_pinned(ctx, sc.L.pinned_bytes + extra_pinned))) return rc;
+    if ((rc = stage_columns(sc))) return rc;
+    DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the pinned buffer may still be read by a previous call's copies
+    return sc.npreds > 0 ? run_predicates(sc, up) : DQ_OK;
+}
+
+// Column c's validity on the device after the predicate stage, nullptr = all valid (validity_source). A host column no
+// predicate reads: only its bitmap goes to the device, into per-call scratch, once per call.
+int column_validity(ScanCall& sc, ScratchBuffers& buf, int c, const uint8_t** v) {
+    dq_ctx* ctx = sc.ctx;
+    const dq_column& col = sc.columns[c];
+    const int src = validity_source(col, sc.use.col_used[c] != 0);
+    if (src == RP_VALID_CALL && !sc.valid[c]) {
+        const size_t bitmap_bytes = (size_t)(sc.nrows + 7) / 8;
+        void* vd = nullptr;
+        DQ_HIP(ctx, buf.alloc(&vd, align_up(bitmap_bytes, 8) + 8));
+        DQ_HIP(ctx, hipMemcpyAsync(vd, col.validity, bitmap_bytes, hipMemcpyHostToDevice, ctx->stream));
+        sc.valid[c] = vd;
+    }
+    *v = src == RP_ONES ? nullptr : src == RP_VALID_DEVICE ? col.validity : (const uint8_t*)sc.valid[c];
+    return DQ_OK;
+}
+
+// The launch arguments of row_outcomes_kernel from the plan's indices and the addresses they name (every RP_VALID_CALL
+// column staged by column_validity before).
+RowOutcomeArgs resolve_row_args(const RowPlan& plan, const ScanCall& sc, const dq_row_term* terms, const dq_row_check* checks) {
+    RowOutcomeArgs args;
+    memset(&args, 0, sizeof(args));
+    args.nterms = (int32_t)plan.term.size();
+    args.nchecks = (int32_t)plan.term_begin.size();
+    args.null_mode = plan.null_mode ? 1 : 0;
+    args.ninline = (int32_t)plan.inl.size();
+    for (int k = 0; k < args.ninline; ++k) {  // the column is one a predicate reads: staged, or read in place
+        const PredTerm& q = plan.inl[k];
+        RowInlineDev& d = args.inl[k];
+        d.values = sc.val[q.col];
+        d.validity = (const uint8_t*)sc.valid[q.col];
+        d.spark_type = sc.columns[q.col].spark_type;
+        d.op = q.op;
+        d.dbl = q.dbl;
+        d.ci = q.ci;
+        d.cd = q.cd;
+    }
+    for (int c = 0; c < args.nchecks; ++c) {
+        args.check[c].pass = (uint64_t*)checks[c].pass_bits;
+        args.check[c].values = checks[c].values;
+        args.check[c].validity = plan.null_mode ? (uint64_t*)checks[c].validity : nullptr;
+        args.check[c].term_begin = plan.term_begin[c];
+        args.check[c].term_end = plan.term_end[c];
+    }
+    for (int i = 0; i < args.nterms; ++i) {
+        const RowPlanTerm& pt = plan.term[i];
+        RowTermDev& td = args.term[i];
+        td.src_inline = -1;
+        td.w_inline = (int16_t)pt.w_inline;
+        td.w = sc.pred_t(pt.where);
+        switch (pt.src) {
+            case RP_BITS:
+                td.src = terms[pt.term].pass_bits;
+                td.src_kind = RS_WORDS;
+                td.w = (const uint64_t*)terms[pt.term].considered_bits;
+                break;
+            case RP_PRED:
+                td.src = sc.pred_t(pt.index);
+                td.src_kind = RS_WORDS;
+                break;
+            case RP_INLINE:
+                td.src_kind = RS_INLINE;
+                td.src_inline = (int16_t)pt.index;
+                break;
+            case RP_VALID_DEVICE:
+                td.src = sc.columns[pt.index].validity;
+                td.src_kind = RS_VALID_BYTES;
+                break;
+            case RP_VALID_SCAN:
+            case RP_VALID_CALL:
+                td.src = sc.valid[pt.index];
+                td.src_kind = RS_VALID_BYTES;
+                break;
+            default:
+                td.src_kind = RS_ONES;
+                break;
+        }
+    }
+    return args;
+}
+
 }  // namespace
 
 namespace dq {
@@ -946,9 +1043,9 @@ int dq_scan(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, con
     return read_back(sc, up, dout, out, flags);
 }
 
-// The filter goes through dq_scan's own stages as the `where` of one Size op planned for the bitmap pass (validate,
-// plan, layout, stage_columns, run_predicates: the TRUE bitmap lands in the arena), then one filter_validity_kernel
-// launch (filter.hip) ANDs it into every target's validity. The scan launch itself is never issued.
+// Stages: argument checks and validate_scan, the predicate-bitmap stage (predicate_bitmaps: the filter's TRUE bitmap
+// lands in the arena), every target's validity (column_validity), then one filter_validity_kernel launch (filter.hip)
+// ANDs the bitmap into them, and the TRUE-row count is read back.
 int dq_filter_validity(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, const dq_predicate* pred,
                        const int32_t* target_columns, int ntargets, uint8_t* const* out_validity_dev, int64_t* true_rows) {
     if (!ctx) return DQ_ERR_INVALID_ARGUMENT;
@@ -972,44 +1069,24 @@ int dq_filter_validity(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t
     }
     DQ_HIP(ctx, hipSetDevice(ctx->device));
 
-    const dq_op op{DQ_OP_SIZE, {-1, -1}, 0, -1};
-    ScanCall sc{ctx, columns, ncols, nrows, &op, 1, pred, 1};
+    const std::vector<dq_op> ops = size_where_ops(1);
+    ScanCall sc{ctx, columns, ncols, nrows, ops.data(), 1, pred, 1};
     std::string msg;
-    int rc = validate_scan(columns, ncols, nrows, &op, 1, pred, 1, &sc.use, &msg);
+    int rc = validate_scan(columns, ncols, nrows, ops.data(), 1, pred, 1, &sc.use, &msg);
     if (rc) return fail(ctx, rc, "%s", msg.c_str());
     if (nrows == 0) return DQ_OK;
     sc.options.where_masks = false;  // the bitmap pass: TRUE / NOT-NULL bitmaps from a predicate launch
     sc.options.pred_vm = pred_vm_forced();
-    rc = plan_scan(columns, ncols, nrows, &op, 1, pred, 1, sc.use, sc.options, &sc.plan, &msg);
-    if (rc) return fail(ctx, rc, "%s", msg.c_str());
-    if ((rc = scan_geometry(sc))) return rc;
-    sc.L = layout_scan(sc.plan, sc.geo, sc.use, columns, ncols, nrows, 1, pred, 1, true);
-    if ((rc = ensure_arena(ctx, sc.L.arena_bytes))) return rc;
-    if ((rc = ensure_pinned(ctx, sc.L.pinned_bytes + 64))) return rc;  // + the TRUE-row count's read-back
-
-    if ((rc = stage_columns(sc))) return rc;
-    DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the pinned buffer may still be read by a previous call's copies
     Stager up{ctx};
-    if ((rc = run_predicates(sc, up))) return rc;
+    if ((rc = predicate_bitmaps(sc, up, 64))) return rc;  // + the TRUE-row count's read-back
 
-    // a host target the predicate does not read: only its bitmap goes to the device
     ScratchBuffers buf(ctx);
-    const size_t bitmap_bytes = (size_t)(nrows + 7) / 8;
     FilterTargets ft;
     memset(&ft, 0, sizeof(ft));
     ft.ntargets = ntargets;
     for (int j = 0; j < ntargets; ++j) {
-        const int c = target_columns[j];
-        const dq_column& col = columns[c];
         ft.out[j] = (uint64_t*)out_validity_dev[j];
-        if ((col.flags & DQ_COL_DEVICE) || sc.use.col_used[c] || !col.validity) {
-            ft.valid[j] = (col.flags & DQ_COL_DEVICE) ? col.validity : (const uint8_t*)sc.valid[c];
-            continue;
-        }
-        void* vd = nullptr;
-        DQ_HIP(ctx, buf.alloc(&vd, align_up(bitmap_bytes, 8) + 8));
-        DQ_HIP(ctx, hipMemcpyAsync(vd, col.validity, bitmap_bytes, hipMemcpyHostToDevice, ctx->stream));
-        ft.valid[j] = (const uint8_t*)vd;
+        if ((rc = column_validity(sc, buf, target_columns[j], &ft.valid[j]))) return rc;
     }
     unsigned long long* dcount = nullptr;
     DQ_HIP(ctx, buf.alloc((void**)&dcount, sizeof(*dcount)));
@@ -1029,13 +1106,13 @@ int dq_filter_validity(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t
     return DQ_OK;
 }
 
-// Every predicate goes through dq_scan's own stages as the `where` of one dummy Size op planned for the bitmap pass, as
-// in dq_filter_validity: run_predicates leaves each TRUE bitmap in the arena, once per predicate however many terms and
-// filters name it, and the scan launch itself is never issued. One row_outcomes_kernel launch (rowlevel.hip) then folds
-// the terms into every check's outputs and the counts. A predicate `column <op> constant` over a numeric column -- the
-// form dq_scan fuses into a value scan -- gets no pass of its own: that launch evaluates it from the column
-// (RowInlineDev, up to kRowInline per call), so the call costs no more predicate launches than the same predicates do as
-// one scan's Compliance ops.
+// Stages: the plan (plan_row_outcomes), the predicate-bitmap stage (predicate_bitmaps: each TRUE bitmap lands in the
+// arena once per predicate, however many terms and filters name it), the host validity bitmaps no predicate reads, the
+// launch arguments (resolve_row_args), then one row_outcomes_kernel launch (rowlevel.hip) folds the terms into every
+// check's outputs and the counts, which are read back in the caller's term order. A predicate `column <op> constant` over
+// a numeric column -- the form dq_scan fuses into a value scan -- gets no pass of its own: that launch evaluates it from
+// the column (RowInlineDev, up to kRowInline per call), so the call costs no more predicate launches than the same
+// predicates do as one scan's Compliance ops.
 int dq_row_outcomes(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nrows, const dq_predicate* preds, int npreds,
                     const dq_row_term* terms, int nterms, const dq_row_check* checks, int nchecks, uint32_t flags,
                     int64_t* term_counts, int64_t* check_counts) {
@@ -1045,166 +1122,29 @@ int dq_row_outcomes(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nr
         (ncols > 0 && !columns) || (npreds > 0 && !preds) || (nterms > 0 && (!terms || !term_counts)))
         return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: invalid arguments");
     if (!ctx->subs.empty()) return fail(ctx, DQ_ERR_UNSUPPORTED, "dq_row_outcomes: multi-device contexts are not supported");
-    if (nterms > DQ_ROW_MAX_TERMS || nchecks > DQ_ROW_MAX_CHECKS)
-        return fail(ctx, DQ_ERR_UNSUPPORTED, "dq_row_outcomes: %d terms over %d checks, at most %d terms and %d checks per call",
-                    nterms, nchecks, DQ_ROW_MAX_TERMS, DQ_ROW_MAX_CHECKS);
-    const bool null_mode = (flags & DQ_ROW_FILTERED_NULL) != 0;
-    for (int t = 0; t < nterms; ++t) {
-        const dq_row_term& tm = terms[t];
-        if (tm.check < 0 || tm.check >= nchecks)
-            return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: term %d names check %d", t, tm.check);
-        if (tm.kind == DQ_ROW_BITS) {
-            if (!tm.pass_bits || !tm.considered_bits)
-                return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: term %d has no bitmaps", t);
-            if (((uintptr_t)tm.pass_bits | (uintptr_t)tm.considered_bits) & 7)
-                return fail(ctx, DQ_ERR_ALIGNMENT, "dq_row_outcomes: bitmaps must be 8-B aligned (term %d)", t);
-            continue;
-        }
-        if (tm.where < -1 || tm.where >= npreds)
-            return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: term %d names predicate %d as its where", t, tm.where);
-        if (tm.kind == DQ_ROW_PREDICATE) {
-            if (tm.index < 0 || tm.index >= npreds)
-                return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: term %d names predicate %d", t, tm.index);
-        } else if (tm.kind == DQ_ROW_NOT_NULL) {
-            if (tm.index < 0 || tm.index >= ncols)
-                return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: term %d names column %d", t, tm.index);
-            const dq_column& col = columns[tm.index];
-            if (col.length != nrows)
-                return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "column %d has %lld rows, batch has %lld", tm.index, (long long)col.length,
-                            (long long)nrows);
-            if ((col.flags & DQ_COL_DEVICE) && ((uintptr_t)col.validity & 7))
-                return fail(ctx, DQ_ERR_ALIGNMENT, "dq_row_outcomes: bitmaps must be 8-B aligned (column %d)", tm.index);
-        } else {
-            return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: term %d has kind %d", t, tm.kind);
-        }
-    }
-    for (int c = 0; c < nchecks; ++c) {
-        const dq_row_check& ck = checks[c];
-        if (!ck.pass_bits || !ck.values || (null_mode && !ck.validity))
-            return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: check %d lacks an output buffer", c);
-        if (((uintptr_t)ck.pass_bits & 7) || ((uintptr_t)ck.values & 15) || (null_mode && ((uintptr_t)ck.validity & 7)))
-            return fail(ctx, DQ_ERR_ALIGNMENT, "dq_row_outcomes: check %d: bitmaps must be 8-B, the byte column 16-B aligned", c);
-    }
+    // every other check, the term order, the inline predicates and every term's source: pure host (call_plans.cpp)
+    RowPlan rp;
+    std::string msg;
+    int rc = plan_row_outcomes(columns, ncols, nrows, preds, npreds, terms, nterms, checks, nchecks, flags, pred_vm_forced(), &rp, &msg);
+    if (rc) return fail(ctx, rc, "%s", msg.c_str());
     for (int t = 0; t < 2 * nterms; ++t) term_counts[t] = 0;
     for (int c = 0; c < 2 * nchecks; ++c) check_counts[c] = 0;
     DQ_HIP(ctx, hipSetDevice(ctx->device));
-
-    std::vector<dq_op> ops((size_t)std::max(npreds, 1));
-    for (int p = 0; p < npreds; ++p) ops[p] = dq_op{DQ_OP_SIZE, {-1, -1}, p, -1};
-    ScanCall sc{ctx, columns, ncols, nrows, ops.data(), npreds, preds, npreds};
-    std::string msg;
-    int rc;
-    if (npreds > 0) {
-        rc = validate_scan(columns, ncols, nrows, ops.data(), npreds, preds, npreds, &sc.use, &msg);
-        if (rc) return fail(ctx, rc, "%s", msg.c_str());
-    } else {
-        sc.use.col_used.assign((size_t)std::max(ncols, 1), 0);
-    }
     if (nrows == 0) return DQ_OK;
-    Stager up{ctx};
-    std::vector<int> inline_of((size_t)std::max(npreds, 1), -1);  // predicate -> inline predicate of the launch
-    PredTerm inline_term[kRowInline];
-    int ninline = 0;
-    if (npreds > 0) {
-        sc.options.where_masks = false;  // the bitmap pass: TRUE / NOT-NULL bitmaps from a predicate launch
-        sc.options.pred_vm = pred_vm_forced();
-        rc = plan_scan(columns, ncols, nrows, ops.data(), npreds, preds, npreds, sc.use, sc.options, &sc.plan, &msg);
-        if (rc) return fail(ctx, rc, "%s", msg.c_str());
-        // `column <op> constant` predicates are evaluated by the row_outcomes launch itself: no pass, no bitmaps
-        for (int p = 0; p < npreds && ninline < kRowInline && !sc.options.pred_vm; ++p) {
-            PredSimple ps;
-            if (!compile_simple_predicate(preds[p], columns, ncols, ps) || ps.nterms != 1 || ps.nb != 1 || ps.b[0] != 0 ||
-                ps.t[0].op < DQ_P_EQ || ps.t[0].op > DQ_P_GE)
-                continue;
-            inline_of[p] = ninline;
-            inline_term[ninline++] = ps.t[0];
-            sc.plan.pred_pass[p] = 0;
-        }
-        if ((rc = scan_geometry(sc))) return rc;
-        sc.L = layout_scan(sc.plan, sc.geo, sc.use, columns, ncols, nrows, npreds, preds, npreds, true);
-        if ((rc = ensure_arena(ctx, sc.L.arena_bytes))) return rc;
-    }
-    const size_t count_bytes = sizeof(unsigned long long) * kRowCounters;
-    if ((rc = ensure_pinned(ctx, (npreds > 0 ? sc.L.pinned_bytes : 0) + count_bytes + 64))) return rc;  // + the counts' read-back
-    if (npreds > 0 && (rc = stage_columns(sc))) return rc;
-    DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the pinned buffer may still be read by a previous call's copies
-    if (npreds > 0 && (rc = run_predicates(sc, up))) return rc;
 
-    // terms sorted by check; a NOT_NULL host column no predicate reads: only its bitmap goes to the device
-    std::vector<int> order((size_t)nterms);
-    for (int t = 0; t < nterms; ++t) order[t] = t;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return terms[a].check < terms[b].check; });
+    const std::vector<dq_op> ops = size_where_ops(npreds);
+    ScanCall sc{ctx, columns, ncols, nrows, ops.data(), npreds, preds, npreds};
+    sc.options = std::move(rp.options);
+    sc.use = std::move(rp.use);
+    const size_t count_bytes = sizeof(unsigned long long) * kRowCounters;
+    Stager up{ctx};
+    if ((rc = predicate_bitmaps(sc, up, count_bytes + 64))) return rc;  // + the counts' read-back
+
     ScratchBuffers buf(ctx);
-    const size_t bitmap_bytes = (size_t)(nrows + 7) / 8;
-    std::vector<const uint8_t*> staged((size_t)std::max(ncols, 1), nullptr);
-    RowOutcomeArgs args;
-    memset(&args, 0, sizeof(args));
-    args.nterms = nterms;
-    args.nchecks = nchecks;
-    args.null_mode = null_mode ? 1 : 0;
-    args.ninline = ninline;
-    for (int k = 0; k < ninline; ++k) {  // the column is one a predicate reads: staged, or read in place
-        const PredTerm& q = inline_term[k];
-        RowInlineDev& d = args.inl[k];
-        d.values = sc.val[q.col];
-        d.validity = (const uint8_t*)sc.valid[q.col];
-        d.spark_type = columns[q.col].spark_type;
-        d.op = q.op;
-        d.dbl = q.dbl;
-        d.ci = q.ci;
-        d.cd = q.cd;
-    }
-    for (int c = 0; c < nchecks; ++c) {
-        args.check[c].pass = (uint64_t*)checks[c].pass_bits;
-        args.check[c].values = checks[c].values;
-        args.check[c].validity = null_mode ? (uint64_t*)checks[c].validity : nullptr;
-    }
-    for (int i = 0, c = 0; c < nchecks; ++c) {
-        args.check[c].term_begin = i;
-        while (i < nterms && terms[order[i]].check == c) ++i;
-        args.check[c].term_end = i;
-    }
-    for (int i = 0; i < nterms; ++i) {
-        const dq_row_term& tm = terms[order[i]];
-        RowTermDev& td = args.term[i];
-        td.src_inline = td.w_inline = -1;
-        if (tm.kind == DQ_ROW_BITS) {
-            td.src = tm.pass_bits;
-            td.src_kind = RS_WORDS;
-            td.w = (const uint64_t*)tm.considered_bits;
-            continue;
-        }
-        if (tm.where >= 0 && inline_of[tm.where] >= 0) td.w_inline = (int16_t)inline_of[tm.where];
-        else td.w = sc.pred_t(tm.where);
-        if (tm.kind == DQ_ROW_PREDICATE) {
-            if (inline_of[tm.index] >= 0) {
-                td.src_kind = RS_INLINE;
-                td.src_inline = (int16_t)inline_of[tm.index];
-            } else {
-                td.src = sc.pred_t(tm.index);
-                td.src_kind = RS_WORDS;
-            }
-            continue;
-        }
-        const int c = tm.index;
-        const dq_column& col = columns[c];
-        const uint8_t* v = nullptr;
-        if (col.flags & DQ_COL_DEVICE) {
-            v = col.validity;
-        } else if (sc.use.col_used[c]) {
-            v = (const uint8_t*)sc.valid[c];
-        } else if (col.validity) {
-            if (!staged[c]) {
-                void* vd = nullptr;
-                DQ_HIP(ctx, buf.alloc(&vd, align_up(bitmap_bytes, 8) + 8));
-                DQ_HIP(ctx, hipMemcpyAsync(vd, col.validity, bitmap_bytes, hipMemcpyHostToDevice, ctx->stream));
-                staged[c] = (const uint8_t*)vd;
-            }
-            v = staged[c];
-        }
-        td.src = v;
-        td.src_kind = v ? RS_VALID_BYTES : RS_ONES;
-    }
+    const uint8_t* v = nullptr;
+    for (const RowPlanTerm& pt : rp.term)
+        if (pt.src == RP_VALID_CALL && (rc = column_validity(sc, buf, pt.index, &v))) return rc;
+    const RowOutcomeArgs args = resolve_row_args(rp, sc, terms, checks);
     unsigned long long* dcounts = nullptr;
     DQ_HIP(ctx, buf.alloc((void**)&dcounts, count_bytes));
     DQ_HIP(ctx, hipMemsetAsync(dcounts, 0, count_bytes, ctx->stream));
@@ -1212,7 +1152,7 @@ int dq_row_outcomes(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nr
         return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: nothing to launch");
     DQ_HIP(ctx, hipGetLastError());
     ctx->kernel_launches[DQ_KERNEL_ROW_OUTCOMES]++;
-    if (npreds > 0 && (rc = check_pred_status(sc, up))) {
+    if ((rc = check_pred_status(sc, up))) {
         (void)hipStreamSynchronize(ctx->stream);  // staged host bitmaps must outlive the kernels
         return rc;
     }
@@ -1221,8 +1161,8 @@ int dq_row_outcomes(dq_ctx* ctx, const dq_column* columns, int ncols, int64_t nr
     DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const unsigned long long* hc = (const unsigned long long*)h;
     for (int i = 0; i < nterms; ++i) {
-        term_counts[2 * order[i]] = (int64_t)hc[2 * i];
-        term_counts[2 * order[i] + 1] = (int64_t)hc[2 * i + 1];
+        term_counts[2 * rp.term[i].term] = (int64_t)hc[2 * i];
+        term_counts[2 * rp.term[i].term + 1] = (int64_t)hc[2 * i + 1];
     }
     for (int c = 0; c < 2 * nchecks; ++c) check_counts[c] = (int64_t)hc[2 * DQ_ROW_MAX_TERMS + c];
     return DQ_OK;
@@ -1438,42 +1378,13 @@ int dq_synth_validity(dq_ctx* ctx, uint64_t seed, int64_t row0, int64_t nrows, i
 // ---- dictionary-encoded STRING columns (dict.hip) ---------------------------------------------------------------------
 namespace {
 
-// DQ_DICT_LDS_ENTRIES=n (read per call): dictionaries of up to n entries count in LDS (at most kDictLdsWords).
-int dict_lds_entries() {
-    const char* e = getenv("DQ_DICT_LDS_ENTRIES");
-    const long v = e ? atol(e) : (long)kDictLdsWords;
-    return (int)std::max<long>(0, std::min<long>(v, kDictLdsWords));
-}
-
-// LDS counter copies of a slot, 0 = global atomics. A workgroup reads at most nrows / grid + 2 tiles of rows, which
-// must stay below 2^31 so that no 32-bit LDS counter can wrap.
-int dict_lds_copies(int n_dict, int64_t nrows, int grid) {
-    if (n_dict <= 0 || n_dict > dict_lds_entries()) return 0;
-    if (nrows / grid + 2 * kDictTileRows >= ((int64_t)1 << 31)) return 0;
-    int c = kDictLdsCopies;
-    if (const char* e = getenv("DQ_DICT_LDS_COPIES")) {  // 1, 2, 4 or 8: fewer copies (measurements)
-        const int v = atoi(e);
-        if (v == 1 || v == 2 || v == 4) c = v;
-    }
-    while (c > 1 && (int64_t)c * n_dict > kDictLdsCopyWords) c >>= 1;
-    return c;
-}
-
-int check_dict_column(dq_ctx* ctx, const dq_dict_column& d, int64_t nrows, int which) {
-    const dq_column& e = d.dictionary;
-    if (!(d.flags & DQ_COL_DEVICE) || !(e.flags & DQ_COL_DEVICE) || (e.flags & DQ_COL_OFFSETS64))
-        return fail(ctx, DQ_ERR_UNSUPPORTED, "dictionary column %d: device buffers with int32 offsets only", which);
-    if (d.length != nrows || nrows < 0 || (nrows > 0 && !d.indices))
-        return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dictionary column %d has %lld rows, batch has %lld", which,
-                    (long long)d.length, (long long)nrows);
-    if (e.spark_type != DQ_TYPE_STRING || e.length < 1 || e.length > INT32_MAX - 1 || !e.offsets || !e.validity || !e.values)
-        return fail(ctx, DQ_ERR_INVALID_ARGUMENT,
-                    "dictionary column %d: the dictionary is a STRING column of n_dict + 1 entries (the last one NULL) "
-                    "with offsets, a validity bitmap and bytes", which);
-    if (((uintptr_t)d.indices & 3) || ((uintptr_t)d.validity & 7) || ((uintptr_t)e.values & 3) ||
-        ((uintptr_t)e.offsets & 3) || ((uintptr_t)e.validity & 7))
-        return fail(ctx, DQ_ERR_ALIGNMENT, "dictionary column %d: misaligned buffer", which);
-    return DQ_OK;
+// DQ_DICT_LDS_ENTRIES=n: dictionaries of up to n entries count in LDS (at most kDictLdsWords); DQ_DICT_LDS_COPIES=1, 2
+// or 4: fewer LDS counter copies (measurements). Read per call.
+DictOptions dict_options() {
+    DictOptions o;
+    if (const char* e = getenv("DQ_DICT_LDS_ENTRIES")) o.lds_entries = (int)std::max<long>(0, std::min<long>(atol(e), kDictLdsWords));
+    if (const char* e = getenv("DQ_DICT_LDS_COPIES")) o.lds_copies = atoi(e);
+    return o;
 }
 
 // One validated predicate of dq_dict_scan: its program pieces in per-call scratch, then the stage dq_scan uses.
@@ -1498,6 +1409,181 @@ void fill_dict_slot(DictSlot& s, const dq_dict_column& d) {
     s.n_dict = (int32_t)(d.dictionary.length - 1);
 }
 
+// A plan slot and the addresses its indices name: zero block, where bitmaps per predicate.
+DictSlot resolve_dict_slot(const DictPlanSlot& ps, const dq_dict_column& d, int64_t* zero, uint64_t* const* wt, uint64_t* const* wn) {
+    DictSlot s;
+    fill_dict_slot(s, d);
+    s.flags = ps.flags;
+    s.stats = zero + ps.stats;
+    s.fold = zero + ps.fold;
+    s.counts = zero + ps.counts;
+    s.hll = (uint32_t*)(zero + ps.hll);
+    s.where_t = ps.where >= 0 ? wt[ps.where] : nullptr;
+    s.where_nn = ps.where >= 0 ? wn[ps.where] : nullptr;
+    s.lds_copies = ps.lds_copies;
+    return s;
+}
+
+// One dq_dict_scan call: its arguments, its plan (call_plans.h) and the per-call scratch the plan's indices resolve to.
+struct DictCall {
+    dq_ctx* ctx;
+    const dq_column* columns;
+    int ncols;
+    const dq_dict_column* dicts;
+    int64_t nrows;
+    const dq_op* ops;
+    int nops;
+    const dq_predicate* preds;
+    int npreds;
+    int grid;
+    DictPlan plan;
+    ScratchBuffers buf;
+    int64_t* zero = nullptr;  // one zeroed block: per slot stats, fold, counts, HLL registers, then the predicate ops' sums
+    DictSlot* dslots = nullptr;
+    DictPredOp* dpops = nullptr;
+    DictOpMap* dops = nullptr;
+    dq_state* dout = nullptr;
+    PredColumn* pcols = nullptr;     // the plain columns, then each predicate op's single column: its slot's dictionary
+    int32_t* status = nullptr;       // one word per predicate, then one per predicate op
+    std::vector<uint64_t*> wt, wn;   // per predicate in use as a where: TRUE / NOT-NULL bitmaps over the rows
+    std::vector<uint64_t*> pt, pn;   // per predicate op: the same over its dictionary's n_dict + 1 entries
+    std::vector<PredColumn> pc;      // host copy of pcols
+    std::vector<DictSlot> slots;     // host copy of dslots
+    int nslots() const { return (int)plan.slots.size(); }
+    int npops() const { return (int)plan.pops.size(); }
+    const dq_column& pop_dictionary(int q) const { return dicts[plan.slots[plan.pops[q].slot].dict].dictionary; }
+};
+
+int alloc_dict_buffers(DictCall& dc) {
+    dq_ctx* ctx = dc.ctx;
+    ScratchBuffers& buf = dc.buf;
+    const int nslots = dc.nslots(), npops = dc.npops(), nops = dc.nops, ncols = dc.ncols, npreds = dc.npreds;
+    DQ_HIP(ctx, buf.alloc((void**)&dc.zero, dc.plan.zwords * 8));
+    DQ_HIP(ctx, buf.alloc((void**)&dc.dslots, sizeof(DictSlot) * nslots));
+    DQ_HIP(ctx, buf.alloc((void**)&dc.dpops, sizeof(DictPredOp) * std::max(npops, 1)));
+    DQ_HIP(ctx, buf.alloc((void**)&dc.dops, sizeof(DictOpMap) * nops));
+    DQ_HIP(ctx, buf.alloc((void**)&dc.dout, sizeof(dq_state) * nops));
+    DQ_HIP(ctx, buf.alloc((void**)&dc.pcols, sizeof(PredColumn) * (size_t)(std::max(ncols, 1) + std::max(npops, 1))));
+    DQ_HIP(ctx, buf.alloc((void**)&dc.status, sizeof(int32_t) * dc.plan.nstatus));
+    const int64_t pwords = padded_words_for(dc.nrows);
+    dc.wt.assign(std::max(npreds, 1), nullptr);
+    dc.wn.assign(std::max(npreds, 1), nullptr);
+    for (int p = 0; p < npreds; ++p) {
+        if (!dc.plan.where_used[p]) continue;
+        DQ_HIP(ctx, buf.alloc((void**)&dc.wt[p], (size_t)pwords * 8));
+        DQ_HIP(ctx, buf.alloc((void**)&dc.wn[p], (size_t)pwords * 8));
+    }
+    dc.pt.assign(std::max(npops, 1), nullptr);
+    dc.pn.assign(std::max(npops, 1), nullptr);
+    for (int q = 0; q < npops; ++q) {
+        const int64_t ew = padded_words_for((int64_t)dc.plan.slots[dc.plan.pops[q].slot].n_dict + 1);
+        DQ_HIP(ctx, buf.alloc((void**)&dc.pt[q], (size_t)ew * 8));
+        DQ_HIP(ctx, buf.alloc((void**)&dc.pn[q], (size_t)ew * 8));
+    }
+    return DQ_OK;
+}
+
+// The zeroed block and status words, the PredColumn records, then the where bitmaps over the plain columns.
+int dict_where_bitmaps(DictCall& dc, Stager& up) {
+    dq_ctx* ctx = dc.ctx;
+    const int ncols = dc.ncols, npops = dc.npops();
+    DQ_HIP(ctx, hipMemsetAsync(dc.zero, 0, dc.plan.zwords * 8, ctx->stream));
+    DQ_HIP(ctx, hipMemsetAsync(dc.status, 0, sizeof(int32_t) * dc.plan.nstatus, ctx->stream));
+    std::vector<PredColumn>& pc = dc.pc;
+    pc.resize(std::max(ncols, 1) + std::max(npops, 1));
+    memset(pc.data(), 0, sizeof(PredColumn) * pc.size());
+    for (int c = 0; c < ncols; ++c) {
+        if (!(dc.columns[c].flags & DQ_COL_DEVICE)) continue;  // unread (checked by the plan)
+        pc[c] = pred_column(dc.columns[c], dc.columns[c].values, dc.columns[c].validity, dc.columns[c].offsets);
+    }
+    for (int q = 0; q < npops; ++q) {
+        const dq_column& e = dc.pop_dictionary(q);
+        PredColumn& pq = pc[std::max(ncols, 1) + q];
+        pq.values = e.values;
+        pq.validity = (const uint64_t*)e.validity;
+        pq.offsets = e.offsets;
+        pq.spark_type = DQ_TYPE_STRING;
+        pq.elem = ET_NONE;
+    }
+    int rc = up.upload(dc.pcols, pc.data(), sizeof(PredColumn) * pc.size());
+    for (int p = 0; p < dc.npreds && !rc; ++p) {
+        if (!dc.plan.where_used[p]) continue;
+        rc = dict_predicate(ctx, up, dc.buf, dc.preds[p], dc.columns, ncols, pc.data(), dc.pcols, dc.nrows, dc.wt[p], dc.wn[p],
+                            dc.status + p);
+    }
+    return rc;
+}
+
+// The per-row pass: every slot in one launch.
+int launch_dict_rows(DictCall& dc, Stager& up) {
+    dq_ctx* ctx = dc.ctx;
+    dc.slots.reserve(dc.nslots());
+    for (const DictPlanSlot& ps : dc.plan.slots)
+        dc.slots.push_back(resolve_dict_slot(ps, dc.dicts[ps.dict], dc.zero, dc.wt.data(), dc.wn.data()));
+    const int rc = up.upload(dc.dslots, dc.slots.data(), sizeof(DictSlot) * dc.nslots());
+    if (rc) return rc;
+    launch_dict_counts(dc.dslots, dc.nslots(), dc.nrows, dc.grid, dc.plan.lds_words, ctx->stream);
+    DQ_HIP(ctx, hipGetLastError());
+    ctx->kernel_launches[DQ_KERNEL_DICT_COUNTS]++;
+    return DQ_OK;
+}
+
+// Per entry: the predicate ops over their dictionaries, then the fold and the states.
+int launch_dict_entries(DictCall& dc, Stager& up) {
+    dq_ctx* ctx = dc.ctx;
+    const int npops = dc.npops(), pc0 = std::max(dc.ncols, 1);
+    std::vector<DictPredOp> pops(std::max(npops, 1));
+    int rc;
+    for (int q = 0; q < npops; ++q) {
+        const dq_column& e = dc.pop_dictionary(q);
+        rc = dict_predicate(ctx, up, dc.buf, dict_pop_predicate(dc.plan, q, dc.preds), &e, 1, dc.pc.data() + pc0 + q,
+                            dc.pcols + pc0 + q, e.length, dc.pt[q], dc.pn[q], dc.status + std::max(dc.npreds, 1) + q);
+        if (rc) return rc;
+        pops[q] = DictPredOp{dc.pt[q], dc.pn[q], (unsigned long long*)(dc.zero + dc.plan.sums_off + 2 * (size_t)q),
+                             dc.plan.pops[q].slot, 0};
+    }
+    std::vector<DictOpMap> opmap = dc.plan.opmap;
+    for (int i = 0; i < dc.nops; ++i)
+        if (dc.plan.op_pop[i] >= 0) opmap[i].sums = pops[dc.plan.op_pop[i]].sums;
+    if (npops && (rc = up.upload(dc.dpops, pops.data(), sizeof(DictPredOp) * npops))) return rc;
+    if ((rc = up.upload(dc.dops, opmap.data(), sizeof(DictOpMap) * dc.nops))) return rc;
+    launch_dict_fold(dc.dslots, dc.nslots(), dc.plan.max_entries, dc.dpops, npops, ctx->stream);
+    DQ_HIP(ctx, hipGetLastError());
+    ctx->kernel_launches[DQ_KERNEL_DICT_FOLD]++;
+    launch_dict_finalize(dc.dslots, dc.dops, dc.nops, dc.nrows, dc.dout, ctx->stream);
+    DQ_HIP(ctx, hipGetLastError());
+    return DQ_OK;
+}
+
+// The states, the status words and every slot's row statistics; the states go to `out` only when nothing failed.
+int dict_read_back(DictCall& dc, Stager& up, dq_state* out) {
+    dq_ctx* ctx = dc.ctx;
+    const int nslots = dc.nslots(), nstatus = dc.plan.nstatus;
+    void *hout = nullptr, *hstatus_ = nullptr;
+    int rc;
+    if ((rc = up.download(&hout, dc.dout, sizeof(dq_state) * dc.nops))) return rc;
+    if ((rc = up.download(&hstatus_, dc.status, sizeof(int32_t) * nstatus))) return rc;
+    const int32_t* hstatus = (const int32_t*)hstatus_;
+    int64_t* hstats = (int64_t*)up.take(sizeof(int64_t) * DS_COUNT * nslots);
+    if (!hstats) return fail(ctx, DQ_ERR_DEVICE, "dq_dict_scan: pinned staging exhausted");
+    for (int s = 0; s < nslots; ++s)
+        DQ_HIP(ctx, hipMemcpyAsync(hstats + DS_COUNT * s, dc.slots[s].stats, sizeof(int64_t) * DS_COUNT, hipMemcpyDeviceToHost, ctx->stream));
+    DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int s = 0; s < nslots; ++s)
+        if (hstats[DS_COUNT * s + DS_BAD_INDEX])
+            return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dictionary column %d: %lld non-NULL rows hold an index outside [0, %d)",
+                        dc.plan.slots[s].dict, (long long)hstats[DS_COUNT * s + DS_BAD_INDEX], dc.slots[s].n_dict);
+    for (int k = 0; k < nstatus; ++k)
+        if (hstatus[k] & 1) return fail(ctx, DQ_ERR_UNSUPPORTED, "dq_dict_scan: regex backtracking limit exceeded");
+    for (int k = 0; k < nstatus; ++k)
+        if (hstatus[k])
+            return fail(ctx, DQ_ERR_UNSUPPORTED,
+                        "dq_dict_scan: a string needs Double.parseDouble's arbitrary-precision path "
+                        "(hexadecimal literal, or > 19 significant digits on a rounding boundary)");
+    memcpy(out, hout, sizeof(dq_state) * dc.nops);
+    return DQ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1507,8 +1593,9 @@ int dq_dict_counts(dq_ctx* ctx, const dq_dict_column* dict, int64_t* counts_dev,
     ctx->err.clear();
     if (!ctx->subs.empty()) return fail(ctx, DQ_ERR_UNSUPPORTED, "dq_dict_counts takes a single-device context");
     const int64_t nrows = dict->length;
-    int rc = check_dict_column(ctx, *dict, nrows, 0);
-    if (rc) return rc;
+    std::string msg;
+    const int rc = check_dict_column(*dict, nrows, 0, &msg);
+    if (rc) return fail(ctx, rc, "%s", msg.c_str());
     DictSlot s;
     fill_dict_slot(s, *dict);
     if ((s.n_dict > 0 && !counts_dev) || ((uintptr_t)counts_dev & 7))
@@ -1522,7 +1609,7 @@ int dq_dict_counts(dq_ctx* ctx, const dq_dict_column* dict, int64_t* counts_dev,
     const int grid = dict_counts_grid(ctx->cus, nrows);
     s.counts = counts_dev;
     s.stats = stats;
-    s.lds_copies = dict_lds_copies(s.n_dict, nrows, grid);
+    s.lds_copies = dict_lds_copies(dict_options(), s.n_dict, nrows, grid);
     DQ_HIP(ctx, hipMemsetAsync(stats, 0, sizeof(int64_t) * DS_COUNT, ctx->stream));
     if (s.n_dict > 0) DQ_HIP(ctx, hipMemsetAsync(counts_dev, 0, sizeof(int64_t) * (size_t)s.n_dict, ctx->stream));
     DQ_HIP(ctx, hipMemcpyAsync(dslot, &s, sizeof(s), hipMemcpyHostToDevice, ctx->stream));
@@ -1549,235 +1636,20 @@ int dq_dict_scan(dq_ctx* ctx, const dq_column* columns, int ncols, const dq_dict
         return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dq_dict_scan: invalid arguments");
     if (nops == 0) return DQ_OK;
     if (!ctx->subs.empty()) return fail(ctx, DQ_ERR_UNSUPPORTED, "dq_dict_scan takes a single-device context");
-    for (int d = 0; d < ndicts; ++d) {
-        const int rc = check_dict_column(ctx, dicts[d], nrows, d);
-        if (rc) return rc;
-    }
-    // ---- plan: one slot per (dictionary column, where); one predicate op per Compliance -------------------------
-    std::map<std::pair<int, int>, int> slot_of;
-    std::vector<DictSlot> slots;
-    std::vector<int> slot_dict, slot_where;
-    std::vector<DictOpMap> opmap(nops);
-    std::vector<int> pop_pred, pop_slot, op_pop(nops, -1);
-    std::vector<char> where_used(std::max(npreds, 1), 0);
-    for (int i = 0; i < nops; ++i) {
-        const dq_op& op = ops[i];
-        const int d = op.column[0] - ncols;
-        if (d < 0 || d >= ndicts) return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "op %d: column %d names no dictionary column", i, op.column[0]);
-        if (op.where < -1 || op.where >= npreds) return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "op %d: bad where index", i);
-        uint32_t flag = 0;
-        switch (op.kind) {
-            case DQ_OP_COMPLETENESS: break;
-            case DQ_OP_MIN_LENGTH: case DQ_OP_MAX_LENGTH: flag = SF_LEN; break;
-            case DQ_OP_DATATYPE: flag = SF_DTYPE; break;
-            case DQ_OP_APPROX_COUNT_DISTINCT: flag = SF_HLL; break;
-            case DQ_OP_COMPLIANCE:
-                if (op.predicate < 0 || op.predicate >= npreds)
-                    return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "op %d: Compliance needs a predicate", i);
-                break;
-            default:
-                return fail(ctx, DQ_ERR_UNSUPPORTED, "op %d: kind %d is not answered from a dictionary column", i, op.kind);
-        }
-        if (op.where >= 0) {
-            where_used[op.where] = 1;
-            const dq_predicate& w = preds[op.where];
-            for (int k = 0; k + 1 < w.code_len; k += 2)
-                if (w.code[k] == DQ_P_COL && (w.code[k + 1] < 0 || w.code[k + 1] >= ncols))
-                    return fail(ctx, DQ_ERR_UNSUPPORTED, "op %d: its where reads a dictionary column", i);
-        }
-        const auto key = std::make_pair(d, (int)op.where);
-        auto it = slot_of.find(key);
-        if (it == slot_of.end()) {
-            DictSlot s;
-            fill_dict_slot(s, dicts[d]);
-            it = slot_of.emplace(key, (int)slots.size()).first;
-            slots.push_back(s);
-            slot_dict.push_back(d);
-            slot_where.push_back(op.where);
-        }
-        slots[it->second].flags |= flag;
-        opmap[i].op = i;
-        opmap[i].kind = op.kind;
-        opmap[i].slot = it->second;
-        opmap[i].has_where = op.where >= 0;
-        opmap[i].sums = nullptr;
-        if (op.kind == DQ_OP_COMPLIANCE) {
-            op_pop[i] = (int)pop_pred.size();
-            pop_pred.push_back(op.predicate);
-            pop_slot.push_back(it->second);
-        }
-    }
-    const int nslots = (int)slots.size(), npops = (int)pop_pred.size();
-    if (nslots > kMaxSlots) return fail(ctx, DQ_ERR_UNSUPPORTED, "dq_dict_scan: more than %d slots", kMaxSlots);
-    for (int c = 0; c < ncols; ++c) {  // the plain columns a where reads
-        bool used = false;
-        for (int p = 0; p < npreds && !used; ++p)
-            for (int k = 0; where_used[p] && k + 1 < preds[p].code_len; k += 2)
-                used |= preds[p].code[k] == DQ_P_COL && preds[p].code[k + 1] == c;
-        if (!used) continue;
-        if (!(columns[c].flags & DQ_COL_DEVICE) || (columns[c].flags & DQ_COL_OFFSETS64) || columns[c].length != nrows ||
-            columns[c].spark_type == DQ_TYPE_DECIMAL128)
-            return fail(ctx, DQ_ERR_UNSUPPORTED, "dq_dict_scan: column %d of a where must be a device column of the batch's rows", c);
-    }
-    // every program as dq_scan validates it, before any launch: the filters over the plain columns, each Compliance
-    // predicate rewritten to read column 0 = its slot's dictionary
-    std::string why;
-    for (int p = 0; p < npreds; ++p) {
-        if (!where_used[p]) continue;
-        const int rc = validate_predicate(preds[p], columns, ncols, &why);
-        if (rc) return fail(ctx, rc, "dq_dict_scan: predicate %d: %s", p, why.c_str());
-    }
-    std::vector<std::vector<int32_t>> pop_code(npops);
-    for (int q = 0; q < npops; ++q) {
-        const dq_predicate& src = preds[pop_pred[q]];
-        if (src.code && src.code_len > 0) pop_code[q].assign(src.code, src.code + src.code_len);
-        for (size_t k = 0; k + 1 < pop_code[q].size(); k += 2)
-            if (pop_code[q][k] == DQ_P_COL) pop_code[q][k + 1] = 0;
-        dq_predicate pr = src;
-        pr.code = src.code ? pop_code[q].data() : nullptr;
-        const int rc = validate_predicate(pr, &dicts[slot_dict[pop_slot[q]]].dictionary, 1, &why);
-        if (rc) return fail(ctx, rc, "dq_dict_scan: predicate %d: %s", pop_pred[q], why.c_str());
-    }
+    // checks, slots, predicate ops, zero-block layout and staging size: pure host (call_plans.cpp)
+    DictCall dc{ctx, columns, ncols, dicts, nrows, ops, nops, preds, npreds, dict_counts_grid(ctx->cus, nrows), {}, ScratchBuffers(ctx)};
+    std::string msg;
+    int rc = plan_dict_scan(columns, ncols, dicts, ndicts, nrows, ops, nops, preds, npreds, dict_options(), dc.grid, &dc.plan, &msg);
+    if (rc) return fail(ctx, rc, "%s", msg.c_str());
     DQ_HIP(ctx, hipSetDevice(ctx->device));
-    const int grid = dict_counts_grid(ctx->cus, nrows);
-    // ---- device buffers --------------------------------------------------------------------------------------
-    ScratchBuffers buf(ctx);
-    size_t zwords = 0;  // one zeroed block: per slot stats, fold, counts, then the predicate ops' sums
-    std::vector<size_t> zoff(nslots);
-    int max_entries = 0;
-    for (int s = 0; s < nslots; ++s) {
-        zoff[s] = zwords;
-        zwords += DS_COUNT + DF_COUNT + (size_t)slots[s].n_dict + kHllRegs / 2;
-        max_entries = std::max(max_entries, slots[s].n_dict);
-    }
-    const size_t sums_off = zwords;
-    zwords += 2 * (size_t)std::max(npops, 1);
-    int64_t* zero = nullptr;
-    DQ_HIP(ctx, buf.alloc((void**)&zero, zwords * 8));
-    DictSlot* dslots = nullptr;
-    DictPredOp* dpops = nullptr;
-    DictOpMap* dops = nullptr;
-    dq_state* dout = nullptr;
-    PredColumn* pcols = nullptr;
-    int32_t* status = nullptr;
-    const int nstatus = std::max(npreds, 1) + std::max(npops, 1);
-    DQ_HIP(ctx, buf.alloc((void**)&dslots, sizeof(DictSlot) * nslots));
-    DQ_HIP(ctx, buf.alloc((void**)&dpops, sizeof(DictPredOp) * std::max(npops, 1)));
-    DQ_HIP(ctx, buf.alloc((void**)&dops, sizeof(DictOpMap) * nops));
-    DQ_HIP(ctx, buf.alloc((void**)&dout, sizeof(dq_state) * nops));
-    DQ_HIP(ctx, buf.alloc((void**)&pcols, sizeof(PredColumn) * (size_t)(std::max(ncols, 1) + std::max(npops, 1))));
-    DQ_HIP(ctx, buf.alloc((void**)&status, sizeof(int32_t) * nstatus));
-    const int64_t pwords = padded_words_for(nrows);
-    std::vector<uint64_t*> wt(std::max(npreds, 1), nullptr), wn(std::max(npreds, 1), nullptr);
-    size_t pin = sizeof(DictSlot) * nslots + sizeof(DictPredOp) * std::max(npops, 1) + sizeof(DictOpMap) * nops +
-                 sizeof(dq_state) * nops + sizeof(PredColumn) * (size_t)(std::max(ncols, 1) + std::max(npops, 1)) +
-                 sizeof(int32_t) * nstatus + sizeof(int64_t) * DS_COUNT * nslots + 4096;
-    for (int p = 0; p < npreds; ++p) {
-        if (!where_used[p]) continue;
-        DQ_HIP(ctx, buf.alloc((void**)&wt[p], (size_t)pwords * 8));
-        DQ_HIP(ctx, buf.alloc((void**)&wn[p], (size_t)pwords * 8));
-        pin += pred_stage_bytes(preds[p]);
-    }
-    std::vector<uint64_t*> pt(std::max(npops, 1), nullptr), pn(std::max(npops, 1), nullptr);
-    for (int q = 0; q < npops; ++q) {
-        const int64_t ew = padded_words_for((int64_t)slots[pop_slot[q]].n_dict + 1);
-        DQ_HIP(ctx, buf.alloc((void**)&pt[q], (size_t)ew * 8));
-        DQ_HIP(ctx, buf.alloc((void**)&pn[q], (size_t)ew * 8));
-        pin += pred_stage_bytes(preds[pop_pred[q]]);
-    }
-    int rc = ensure_pinned(ctx, pin);
-    if (rc) return rc;
+    if ((rc = alloc_dict_buffers(dc))) return rc;
+    if ((rc = ensure_pinned(ctx, dc.plan.pinned_bytes))) return rc;
     DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the pinned buffer may still feed a previous call's copies
     Stager up{ctx};
-    DQ_HIP(ctx, hipMemsetAsync(zero, 0, zwords * 8, ctx->stream));
-    DQ_HIP(ctx, hipMemsetAsync(status, 0, sizeof(int32_t) * nstatus, ctx->stream));
-    // ---- the where bitmaps over the plain columns ----------------------------------------------------------------
-    std::vector<PredColumn> pc(std::max(ncols, 1) + std::max(npops, 1));
-    memset(pc.data(), 0, sizeof(PredColumn) * pc.size());
-    for (int c = 0; c < ncols; ++c) {
-        if (!(columns[c].flags & DQ_COL_DEVICE)) continue;  // unread (checked above)
-        pc[c] = pred_column(columns[c], columns[c].values, columns[c].validity, columns[c].offsets);
-    }
-    const int pc0 = std::max(ncols, 1);
-    for (int q = 0; q < npops; ++q) {  // each predicate op's single column: its slot's dictionary
-        const dq_column& e = dicts[slot_dict[pop_slot[q]]].dictionary;
-        pc[pc0 + q].values = e.values;
-        pc[pc0 + q].validity = (const uint64_t*)e.validity;
-        pc[pc0 + q].offsets = e.offsets;
-        pc[pc0 + q].spark_type = DQ_TYPE_STRING;
-        pc[pc0 + q].elem = ET_NONE;
-    }
-    if ((rc = up.upload(pcols, pc.data(), sizeof(PredColumn) * pc.size()))) return rc;
-    for (int p = 0; p < npreds; ++p) {
-        if (!where_used[p]) continue;
-        rc = dict_predicate(ctx, up, buf, preds[p], columns, ncols, pc.data(), pcols, nrows, wt[p], wn[p], status + p);
-        if (rc) return rc;
-    }
-    // ---- the per-row pass: every slot in one launch --------------------------------------------------------------
-    int lds_words = 0;
-    for (int s = 0; s < nslots; ++s) {
-        int64_t* base = zero + zoff[s];
-        slots[s].stats = base;
-        slots[s].fold = base + DS_COUNT;
-        slots[s].counts = base + DS_COUNT + DF_COUNT;
-        slots[s].hll = (uint32_t*)(base + DS_COUNT + DF_COUNT + slots[s].n_dict);
-        slots[s].where_t = slot_where[s] >= 0 ? wt[slot_where[s]] : nullptr;
-        slots[s].where_nn = slot_where[s] >= 0 ? wn[slot_where[s]] : nullptr;
-        slots[s].lds_copies = dict_lds_copies(slots[s].n_dict, nrows, grid);
-        lds_words = std::max(lds_words, slots[s].lds_copies * slots[s].n_dict);
-    }
-    if ((rc = up.upload(dslots, slots.data(), sizeof(DictSlot) * nslots))) return rc;
-    launch_dict_counts(dslots, nslots, nrows, grid, lds_words, ctx->stream);
-    DQ_HIP(ctx, hipGetLastError());
-    ctx->kernel_launches[DQ_KERNEL_DICT_COUNTS]++;
-    // ---- per entry: predicates over the dictionaries, then the fold ----------------------------------------------
-    std::vector<DictPredOp> pops(std::max(npops, 1));
-    for (int q = 0; q < npops; ++q) {
-        dq_predicate pr = preds[pop_pred[q]];
-        pr.code = pop_code[q].data();  // reads column 0: the dictionary
-        const dq_column& e = dicts[slot_dict[pop_slot[q]]].dictionary;
-        rc = dict_predicate(ctx, up, buf, pr, &e, 1, pc.data() + pc0 + q, pcols + pc0 + q, e.length, pt[q], pn[q],
-                            status + std::max(npreds, 1) + q);
-        if (rc) return rc;
-        pops[q].pred_t = pt[q];
-        pops[q].pred_nn = pn[q];
-        pops[q].sums = (unsigned long long*)(zero + sums_off + 2 * (size_t)q);
-        pops[q].slot = pop_slot[q];
-        pops[q].pad = 0;
-    }
-    for (int i = 0; i < nops; ++i)
-        if (op_pop[i] >= 0) opmap[i].sums = pops[op_pop[i]].sums;
-    if (npops && (rc = up.upload(dpops, pops.data(), sizeof(DictPredOp) * npops))) return rc;
-    if ((rc = up.upload(dops, opmap.data(), sizeof(DictOpMap) * nops))) return rc;
-    launch_dict_fold(dslots, nslots, max_entries, dpops, npops, ctx->stream);
-    DQ_HIP(ctx, hipGetLastError());
-    ctx->kernel_launches[DQ_KERNEL_DICT_FOLD]++;
-    launch_dict_finalize(dslots, dops, nops, nrows, dout, ctx->stream);
-    DQ_HIP(ctx, hipGetLastError());
-    // ---- results ---------------------------------------------------------------------------------------------
-    void *hout_ = nullptr, *hstatus_ = nullptr;
-    if ((rc = up.download(&hout_, dout, sizeof(dq_state) * nops))) return rc;
-    if ((rc = up.download(&hstatus_, status, sizeof(int32_t) * nstatus))) return rc;
-    const dq_state* hout = (const dq_state*)hout_;
-    const int32_t* hstatus = (const int32_t*)hstatus_;
-    int64_t* hstats = (int64_t*)up.take(sizeof(int64_t) * DS_COUNT * nslots);
-    if (!hstats) return fail(ctx, DQ_ERR_DEVICE, "dq_dict_scan: pinned staging exhausted");
-    for (int s = 0; s < nslots; ++s)
-        DQ_HIP(ctx, hipMemcpyAsync(hstats + DS_COUNT * s, slots[s].stats, sizeof(int64_t) * DS_COUNT, hipMemcpyDeviceToHost, ctx->stream));
-    DQ_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int s = 0; s < nslots; ++s)
-        if (hstats[DS_COUNT * s + DS_BAD_INDEX])
-            return fail(ctx, DQ_ERR_INVALID_ARGUMENT, "dictionary column %d: %lld non-NULL rows hold an index outside [0, %d)",
-                        slot_dict[s], (long long)hstats[DS_COUNT * s + DS_BAD_INDEX], slots[s].n_dict);
-    for (int k = 0; k < nstatus; ++k)
-        if (hstatus[k] & 1) return fail(ctx, DQ_ERR_UNSUPPORTED, "dq_dict_scan: regex backtracking limit exceeded");
-    for (int k = 0; k < nstatus; ++k)
-        if (hstatus[k])
-            return fail(ctx, DQ_ERR_UNSUPPORTED,
-                        "dq_dict_scan: a string needs Double.parseDouble's arbitrary-precision path "
-                        "(hexadecimal literal, or > 19 significant digits on a rounding boundary)");
-    memcpy(out, hout, sizeof(dq_state) * nops);
-    return DQ_OK;
+    if ((rc = dict_where_bitmaps(dc, up))) return rc;
+    if ((rc = launch_dict_rows(dc, up))) return rc;
+    if ((rc = launch_dict_entries(dc, up))) return rc;
+    return dict_read_back(dc, up, out);
 }
 
 }  // extern "C"

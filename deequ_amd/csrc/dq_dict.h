@@ -1,7 +1,10 @@
-// dq_dict.h — layouts shared by the host runtime (dq_api.cpp) and the dictionary kernels (dict.hip).
+// dq_dict.h — layouts shared by the host runtime (dq_api.cpp, call_plans.cpp) and the dictionary kernels (dict.hip).
+// The layouts compile without HIP (-DDQ_HOST_ONLY, as dq_internal.h); the launchers after them need the HIP runtime.
 #pragma once
 
+#if !defined(DQ_HOST_ONLY)
 #include <hip/hip_runtime.h>
+#endif
 #include <stdint.h>
 
 #include "dq_internal.h"
@@ -55,11 +58,13 @@ struct DictOpMap {
     const unsigned long long* sums;  // DQ_OP_COMPLIANCE: its DictPredOp's sums
 };
 
+#if !defined(DQ_HOST_ONLY)
 int dict_counts_grid(int cus, int64_t nrows);
 void launch_dict_counts(const DictSlot* slots, int nslots, int64_t nrows, int grid, int lds_words, hipStream_t s);
 void launch_dict_fold(const DictSlot* slots, int nslots, int max_entries, const DictPredOp* pops, int npops,
                       hipStream_t s);
 void launch_dict_finalize(const DictSlot* slots, const DictOpMap* ops, int nops, int64_t nrows, dq_state* out,
                           hipStream_t s);
+#endif  // !DQ_HOST_ONLY
 
 }  // namespace dq

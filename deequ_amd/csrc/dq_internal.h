@@ -10,7 +10,7 @@
 // PredColumn) are built from a plan record and the arena layout only once every device address is known, each by one
 // resolve function of dq_api.cpp that fills a fresh struct; no descriptor field ever holds an index.
 //
-// The layouts up to rows_per_load_of compile without HIP (-DDQ_HOST_ONLY: scan_plan.cpp under the host sanitizers);
+// The layouts up to rows_per_load_of compile without HIP (-DDQ_HOST_ONLY: scan_plan.cpp and call_plans.cpp under the host sanitizers);
 // the context, the scratch helpers and the kernel launchers after them need the HIP runtime.
 #pragma once
 

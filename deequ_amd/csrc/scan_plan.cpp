@@ -13,8 +13,6 @@
 
 namespace dq {
 
-namespace {
-
 int failf(std::string* msg, int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
@@ -24,6 +22,8 @@ int failf(std::string* msg, int code, const char* fmt, ...) {
     if (msg) *msg = buf;
     return code;
 }
+
+namespace {
 
 bool is_numeric_type(int t) {
     // Preconditions.isNumeric (A/Analyzer.scala:329-343)
@@ -196,6 +196,11 @@ int validate_scan(const dq_column* columns, int ncols, int64_t nrows, const dq_o
         if (rc) return failf(msg, rc, "predicate %d: %s", p, why.c_str());
     }
     return DQ_OK;
+}
+
+size_t pred_stage_bytes(const dq_predicate& pr) {
+    return align_up(sizeof(PredProgram), 16) + align_up(sizeof(int32_t) * (size_t)pr.code_len, 16) +
+           align_up(sizeof(dq_const) * (size_t)std::max(pr.n_consts, 0), 16) + align_up((size_t)std::max<int64_t>(pr.strings_len, 0), 16);
 }
 
 bool compile_simple_predicate(const dq_predicate& pr, const dq_column* columns, int ncols, PredSimple& out) {
@@ -737,6 +742,8 @@ int plan_scan(const dq_column* columns, int ncols, int64_t nrows, const dq_op* o
         plan.pred_pass[p] = 0;
         if (!plan.where[p].bitmaps) plan.pred_used[p] = 0;
     }
+    for (size_t p = 0; p < options.pred_inline.size(); ++p)
+        if (options.pred_inline[p]) plan.pred_used[p] = plan.pred_pass[p] = 0;
     plan_groups(plan);
     return DQ_OK;
 }

@@ -24,6 +24,9 @@ struct ScanOptions {
     bool where_masks = true;     // simple `where` filters are evaluated inside the scan (WhereOut)
     bool fused_producer = true;  // ... by the scan of the filter's own column where that is possible
     bool pred_vm = false;        // every predicate on the general VM: no masks, no simple-predicate kernel
+    // Not from the environment: predicates the caller's own kernel evaluates from their column (dq_row_outcomes), which
+    // get neither bitmaps nor a pass; their columns stay staged. Empty: none.
+    std::vector<char> pred_inline;
 };
 
 // Which columns / predicates the call reads, and which ops go to the decimal128 launch (validate_scan).
@@ -134,11 +137,15 @@ struct ScanLayout {
     size_t pinned_bytes = 0;  // staging for every upload and read-back of the call
 };
 
+// Returns `code` with the formatted message in *msg: how every plan function refuses a call.
+int failf(std::string* msg, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
 // DQ_OK, or the error code with its message in *msg (without the "predicate %d: " prefix). col_used (may be null):
 // set for every column the program reads.
 int validate_predicate(const dq_predicate& pr, const dq_column* columns, int ncols, std::string* msg, char* col_used = nullptr);
 int validate_scan(const dq_column* columns, int ncols, int64_t nrows, const dq_op* ops, int nops, const dq_predicate* preds,
                   int npreds, ScanUse* use, std::string* msg);
+// Pinned staging bytes of one predicate's program pieces, as run_predicate uploads them.
+size_t pred_stage_bytes(const dq_predicate& pr);
 // Recognises the predicates pred_simple_kernel evaluates (see PredSimple): a symbolic run of the postfix program.
 bool compile_simple_predicate(const dq_predicate& pr, const dq_column* columns, int ncols, PredSimple& out);
 // Of a validated call. DQ_ERR_UNSUPPORTED when it needs more than kMaxSlots slots.

@@ -2,6 +2,8 @@
 // validate_scan -> plan_scan -> plan_geometry -> layout_scan checked field by field against the rules of dq_scan,
 // and validate_predicate over rejected examples and 20 000 seeded random programs on exactly-sized heap buffers.
 // Column buffers are presence flags only: nothing here is ever dereferenced by the plan.
+// The same for the plans of dq_row_outcomes and dq_dict_scan (call_plans.cpp): plan_row_outcomes, plan_dict_scan,
+// dict_lds_copies and every refusal's code and text.
 // Built and run by tests/test_scan_plan.py; prints "scan_plan_checks: ok" and exits 0 when every check holds.
 #include <stdio.h>
 #include <stdlib.h>
@@ -12,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "call_plans.h"
 #include "scan_plan.h"
 
 using namespace dq;
@@ -612,6 +615,454 @@ static void case14_random_programs() {
     CHECK(accepted >= 200);  // the property above is not vacuous
 }
 
+// ---- plan_row_outcomes (call_plans.cpp) -----------------------------------------------------------------------------------
+static dq_column host_column(int type, bool validity, int64_t nrows) {
+    dq_column c = column(type, validity, nrows);
+    c.flags = 0;
+    return c;
+}
+static dq_row_term row_term(int kind, int index, int where, int check) {
+    dq_row_term t;
+    memset(&t, 0, sizeof(t));
+    t.kind = kind;
+    t.index = index;
+    t.where = where;
+    t.check = check;
+    if (kind == DQ_ROW_BITS) t.pass_bits = t.considered_bits = (const uint8_t*)g_present;
+    return t;
+}
+static dq_row_check row_check() {
+    dq_row_check c;
+    c.pass_bits = c.values = c.validity = (uint8_t*)g_present;
+    return c;
+}
+struct RowRun {
+    int rc = 0;
+    std::string msg;
+    RowPlan plan;
+};
+static RowRun row_run(const std::vector<dq_column>& cols, int64_t nrows, const std::vector<Pred>& preds,
+                      const std::vector<dq_row_term>& terms, const std::vector<dq_row_check>& checks, uint32_t flags = 0,
+                      bool pred_vm = false) {
+    std::vector<dq_predicate> pv;
+    for (const Pred& p : preds) pv.push_back(p.view());
+    RowRun r;
+    r.rc = plan_row_outcomes(cols.data(), (int)cols.size(), nrows, pv.data(), (int)pv.size(), terms.data(), (int)terms.size(),
+                             checks.data(), (int)checks.size(), flags, pred_vm, &r.plan, &r.msg);
+    return r;
+}
+static void expect_row_reject(const RowRun& r, int code, const char* text) {
+    if (r.rc != code || r.msg != text) {
+        ++g_failed;
+        printf("FAILED: expected %d \"%s\", got %d \"%s\"\n", code, text, r.rc, r.msg.c_str());
+    }
+}
+
+static void case15_row_term_order() {
+    const int check_of[] = {2, 0, 1, 0, 2, 1, 0};
+    std::vector<dq_row_term> terms;
+    for (int c : check_of) terms.push_back(row_term(DQ_ROW_NOT_NULL, K, -1, c));
+    const RowRun r = row_run(table(kRows), kRows, {}, terms, {row_check(), row_check(), row_check()});
+    CHECK(r.rc == DQ_OK);
+    const RowPlan& p = r.plan;
+    CHECK(p.term.size() == terms.size() && p.term_begin.size() == 3 && p.term_end.size() == 3);
+    CHECK(p.term_begin[0] == 0 && p.term_end[2] == (int)terms.size());  // the ranges partition the sorted terms
+    for (int c = 0; c < 3; ++c) {
+        if (c > 0) CHECK(p.term_begin[c] == p.term_end[c - 1]);
+        CHECK(p.term_end[c] - p.term_begin[c] == (c == 0 ? 3 : 2));
+        for (int i = p.term_begin[c]; i < p.term_end[c]; ++i) {
+            CHECK(terms[p.term[i].term].check == c);
+            if (i > p.term_begin[c]) CHECK(p.term[i].term > p.term[i - 1].term);  // stable
+        }
+    }
+    // the read-back: counter pair i goes to the caller's term p.term[i].term, every term exactly once
+    std::vector<int64_t> counts(2 * terms.size(), -1);
+    for (size_t i = 0; i < p.term.size(); ++i) {
+        CHECK(counts[2 * p.term[i].term] == -1);
+        counts[2 * p.term[i].term] = 100 + (int64_t)i;
+        counts[2 * p.term[i].term + 1] = 200 + (int64_t)i;
+    }
+    for (size_t t = 0; t < terms.size(); ++t) {
+        const int64_t i = counts[2 * t] - 100;
+        CHECK(i >= p.term_begin[check_of[t]] && i < p.term_end[check_of[t]] && counts[2 * t + 1] == 200 + i);
+    }
+}
+
+static void case16_row_inline() {
+    std::vector<Pred> preds;
+    for (int i = 0; i < kRowInline + 1; ++i) preds.push_back(compare(K, DQ_P_LT, i));
+    std::vector<dq_predicate> pv;
+    for (const Pred& p : preds) pv.push_back(p.view());
+    const std::vector<dq_row_term> terms = {row_term(DQ_ROW_PREDICATE, 0, 1, 0), row_term(DQ_ROW_PREDICATE, kRowInline, kRowInline, 0)};
+    for (int vm = 0; vm < 2; ++vm) {
+        std::vector<dq_column> cols = table(kRows);
+        cols[K] = host_column(DQ_TYPE_LONG, true, kRows);  // an inline predicate's column is still staged
+        const RowRun r = row_run(cols, kRows, preds, terms, {row_check()}, 0, vm != 0);
+        CHECK(r.rc == DQ_OK);
+        const RowPlan& p = r.plan;
+        CHECK((int)p.inl.size() == (vm ? 0 : kRowInline));  // exactly 16 inline; none under pred_vm
+        CHECK(p.use.col_used[K] == 1);
+        for (int i = 0; i <= kRowInline; ++i) {
+            const bool inl = !vm && i < kRowInline;
+            CHECK(p.inline_of[i] == (inl ? i : -1));
+            CHECK(p.options.pred_inline[i] == (inl ? 1 : 0));
+            if (inl) CHECK(p.inl[i].col == K && p.inl[i].op == DQ_P_LT && p.inl[i].ci == i);
+        }
+        CHECK(!p.options.where_masks && p.options.pred_vm == (vm != 0));
+        // the scan plan, made once: the 17th gets a pass, an inline predicate neither a pass nor bitmaps
+        const std::vector<dq_op> ops = size_where_ops((int)pv.size());
+        ScanPlan sp;
+        std::string msg;
+        CHECK(plan_scan(cols.data(), (int)cols.size(), kRows, ops.data(), (int)ops.size(), pv.data(), (int)pv.size(), p.use, p.options,
+                        &sp, &msg) == DQ_OK);
+        for (int i = 0; i <= kRowInline; ++i) {
+            const bool inl = !vm && i < kRowInline;
+            CHECK(sp.pred_pass[i] == (inl ? 0 : 1) && sp.pred_used[i] == (inl ? 0 : 1));
+        }
+        CHECK(p.term[0].src == (vm ? RP_PRED : RP_INLINE) && p.term[0].index == 0);
+        CHECK(p.term[0].w_inline == (vm ? -1 : 1) && p.term[0].where == (vm ? 1 : -1));
+        CHECK(p.term[1].src == RP_PRED && p.term[1].index == kRowInline && p.term[1].where == kRowInline && p.term[1].w_inline == -1);
+    }
+    const RowRun c = row_run(table(kRows), kRows, {d_and_k()}, {row_term(DQ_ROW_PREDICATE, 0, -1, 0)}, {row_check()});
+    CHECK(c.rc == DQ_OK && c.plan.inl.empty() && c.plan.inline_of[0] == -1);  // a compound predicate is never inline
+    CHECK(c.plan.term[0].src == RP_PRED && c.plan.term[0].index == 0 && c.plan.term[0].where == -1);
+}
+
+static void case17_row_sources() {
+    // 0: device, 1: host and read by the predicate, 2: host, read by nobody, 3: the same without validity, 4: device without
+    const std::vector<dq_column> cols = {column(DQ_TYPE_LONG, true, kRows), host_column(DQ_TYPE_LONG, true, kRows),
+                                         host_column(DQ_TYPE_LONG, true, kRows), host_column(DQ_TYPE_LONG, false, kRows),
+                                         column(DQ_TYPE_LONG, false, kRows)};
+    std::vector<dq_row_term> terms = {row_term(DQ_ROW_BITS, 0, 0, 0)};
+    for (int c = 0; c < 5; ++c) terms.push_back(row_term(DQ_ROW_NOT_NULL, c, -1, 0));
+    Pred both = d_and_k();  // compound: reads columns 1 and 1
+    both.code[1] = both.code[7] = 1;
+    const RowRun r = row_run(cols, kRows, {both}, terms, {row_check()}, DQ_ROW_FILTERED_NULL);
+    CHECK(r.rc == DQ_OK && r.plan.null_mode);
+    const RowPlan& p = r.plan;
+    CHECK(p.term[0].src == RP_BITS && p.term[0].term == 0 && p.term[0].where == -1 && p.term[0].w_inline == -1);
+    const int want[] = {RP_VALID_DEVICE, RP_VALID_SCAN, RP_VALID_CALL, RP_ONES, RP_ONES};
+    for (int c = 0; c < 5; ++c) CHECK(p.term[1 + c].src == want[c] && p.term[1 + c].index == c && p.term[1 + c].where == -1);
+    CHECK(validity_source(cols[2], true) == RP_VALID_SCAN && validity_source(cols[0], false) == RP_VALID_DEVICE);
+    // without predicates nothing is validated as a scan's column and nothing is read by one
+    const RowRun n = row_run(cols, kRows, {}, {row_term(DQ_ROW_NOT_NULL, 1, -1, 0)}, {row_check()});
+    CHECK(n.rc == DQ_OK && n.plan.term[0].src == RP_VALID_CALL && n.plan.inl.empty());
+}
+
+static void case18_row_refusals() {
+    const std::vector<dq_column> cols = table(kRows);
+    const std::vector<Pred> preds = {compare(K, DQ_P_LT, 25)};
+    const std::vector<dq_row_check> one = {row_check()};
+    auto reject = [&](const dq_row_term& t, int code, const char* text) { expect_row_reject(row_run(cols, kRows, preds, {t}, one), code, text); };
+    reject(row_term(DQ_ROW_NOT_NULL, K, -1, 3), DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: term 0 names check 3");
+    reject(row_term(DQ_ROW_NOT_NULL, K, -1, -1), DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: term 0 names check -1");
+    reject(row_term(DQ_ROW_PREDICATE, 5, -1, 0), DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: term 0 names predicate 5");
+    reject(row_term(DQ_ROW_NOT_NULL, 99, -1, 0), DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: term 0 names column 99");
+    reject(row_term(DQ_ROW_NOT_NULL, K, 7, 0), DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: term 0 names predicate 7 as its where");
+    reject(row_term(DQ_ROW_NOT_NULL, K, -2, 0), DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: term 0 names predicate -2 as its where");
+    reject(row_term(9, K, -1, 0), DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: term 0 has kind 9");
+    dq_row_term bits = row_term(DQ_ROW_BITS, 0, 0, 0);
+    bits.considered_bits = nullptr;
+    reject(bits, DQ_ERR_INVALID_ARGUMENT, "dq_row_outcomes: term 0 has no bitmaps");
+    bits.considered_bits = (const uint8_t*)g_present + 4;
+    reject(bits, DQ_ERR_ALIGNMENT, "dq_row_outcomes: bitmaps must be 8-B aligned (term 0)");
+    // output buffers
+    const dq_row_term ok = row_term(DQ_ROW_NOT_NULL, K, -1, 0);
+    const char* lacks = "dq_row_outcomes: check 0 lacks an output buffer";
+    const char* misaligned = "dq_row_outcomes: check 0: bitmaps must be 8-B, the byte column 16-B aligned";
+    dq_row_check ck = row_check();
+    ck.pass_bits = nullptr;
+    expect_row_reject(row_run(cols, kRows, preds, {ok}, {ck}), DQ_ERR_INVALID_ARGUMENT, lacks);
+    ck = row_check();
+    ck.values = nullptr;
+    expect_row_reject(row_run(cols, kRows, preds, {ok}, {ck}), DQ_ERR_INVALID_ARGUMENT, lacks);
+    ck = row_check();
+    ck.validity = nullptr;
+    CHECK(row_run(cols, kRows, preds, {ok}, {ck}).rc == DQ_OK);  // read in null mode only
+    expect_row_reject(row_run(cols, kRows, preds, {ok}, {ck}, DQ_ROW_FILTERED_NULL), DQ_ERR_INVALID_ARGUMENT, lacks);
+    ck = row_check();
+    ck.pass_bits = (uint8_t*)g_present + 4;
+    expect_row_reject(row_run(cols, kRows, preds, {ok}, {ck}), DQ_ERR_ALIGNMENT, misaligned);
+    ck = row_check();
+    ck.values = (uint8_t*)g_present + 8;
+    expect_row_reject(row_run(cols, kRows, preds, {ok}, {ck}), DQ_ERR_ALIGNMENT, misaligned);
+    ck = row_check();
+    ck.validity = (uint8_t*)g_present + 4;
+    CHECK(row_run(cols, kRows, preds, {ok}, {ck}).rc == DQ_OK);
+    expect_row_reject(row_run(cols, kRows, preds, {ok}, {ck}, DQ_ROW_FILTERED_NULL), DQ_ERR_ALIGNMENT, misaligned);
+    // a NOT_NULL column: device validity 8-B aligned, as many rows as the batch
+    std::vector<dq_column> bad = cols;
+    bad[L].validity = (const uint8_t*)g_present + 4;
+    expect_row_reject(row_run(bad, kRows, {}, {row_term(DQ_ROW_NOT_NULL, L, -1, 0)}, one), DQ_ERR_ALIGNMENT,
+                      "dq_row_outcomes: bitmaps must be 8-B aligned (column 1)");
+    bad = cols;
+    bad[L].length = 5;
+    expect_row_reject(row_run(bad, kRows, {}, {row_term(DQ_ROW_NOT_NULL, L, -1, 0)}, one), DQ_ERR_INVALID_ARGUMENT,
+                      "column 1 has 5 rows, batch has 50001");
+    // the predicates as dq_scan validates them
+    Pred broken = compare(K, DQ_P_LT, 25);
+    broken.code[1] = 99;
+    expect_row_reject(row_run(cols, kRows, {broken}, {ok}, one), DQ_ERR_PREDICATE, "predicate 0: bad column 99");
+    // more than a launch takes
+    const std::vector<dq_row_term> many(DQ_ROW_MAX_TERMS + 1, ok);
+    expect_row_reject(row_run(cols, kRows, preds, many, one), DQ_ERR_UNSUPPORTED,
+                      "dq_row_outcomes: 65 terms over 1 checks, at most 64 terms and 16 checks per call");
+    expect_row_reject(row_run(cols, kRows, preds, {ok}, std::vector<dq_row_check>(DQ_ROW_MAX_CHECKS + 1, row_check())), DQ_ERR_UNSUPPORTED,
+                      "dq_row_outcomes: 1 terms over 17 checks, at most 64 terms and 16 checks per call");
+    CHECK(row_run(cols, kRows, preds, std::vector<dq_row_term>(DQ_ROW_MAX_TERMS, ok),
+                  std::vector<dq_row_check>(DQ_ROW_MAX_CHECKS, row_check())).rc == DQ_OK);
+}
+
+// ---- plan_dict_scan, dict_lds_copies (call_plans.cpp) ----------------------------------------------------------------------
+static dq_dict_column dict_column(int n_dict, int64_t nrows) {
+    dq_dict_column d;
+    memset(&d, 0, sizeof(d));
+    d.flags = DQ_COL_DEVICE;
+    d.length = nrows;
+    d.indices = (const int32_t*)g_present;
+    d.validity = (const uint8_t*)g_present;
+    d.dictionary = column(DQ_TYPE_STRING, true, (int64_t)n_dict + 1);
+    return d;
+}
+struct DictRun {
+    int rc = 0;
+    std::string msg;
+    DictPlan plan;
+};
+static DictRun dict_run(const std::vector<dq_column>& cols, const std::vector<dq_dict_column>& dicts, int64_t nrows,
+                        const std::vector<dq_op>& ops, const std::vector<Pred>& preds) {
+    std::vector<dq_predicate> pv;
+    for (const Pred& p : preds) pv.push_back(p.view());
+    DictRun r;
+    r.rc = plan_dict_scan(cols.data(), (int)cols.size(), dicts.data(), (int)dicts.size(), nrows, ops.data(), (int)ops.size(), pv.data(),
+                          (int)pv.size(), DictOptions(), 64, &r.plan, &r.msg);
+    return r;
+}
+static void expect_dict_reject(const DictRun& r, int code, const char* text) {
+    if (r.rc != code || r.msg != text) {
+        ++g_failed;
+        printf("FAILED: expected %d \"%s\", got %d \"%s\"\n", code, text, r.rc, r.msg.c_str());
+    }
+}
+// entry = 'abc'-shaped: [COL c, CONST 0, EQ]
+static Pred entry_equals(int col) {
+    Pred p = compare(col, DQ_P_EQ, 0);
+    p.consts = {string_const(0, 3)};
+    p.strings = {'a', 'b', 'c'};
+    return p;
+}
+static size_t up16(size_t n) { return (n + 15) / 16 * 16; }
+// The staging of one run_predicate, from the uploads it makes (an empty piece is not uploaded).
+static size_t program_staging(const Pred& p) {
+    return up16(4 * p.code.size()) + (p.consts.empty() ? 0 : up16(sizeof(dq_const) * p.consts.size())) +
+           (p.strings.empty() ? 0 : up16(p.strings.size())) + up16(sizeof(PredProgram));
+}
+
+static void case19_dict_plan() {
+    const std::vector<dq_column> cols = table(kRows);
+    const std::vector<dq_dict_column> dicts = {dict_column(64, kRows), dict_column(1000, kRows)};
+    const int D0 = NCOLS, D1 = NCOLS + 1;
+    const std::vector<Pred> preds = {compare(K, DQ_P_LT, 25), d_and_k(), entry_equals(D1)};
+    const std::vector<int32_t> callers_code = preds[2].code;
+    const std::vector<dq_op> ops = {op(DQ_OP_MIN_LENGTH, D0),       op(DQ_OP_DATATYPE, D0),          op(DQ_OP_COMPLETENESS, D0, 0),
+                                    op(DQ_OP_MAX_LENGTH, D0, 1),    op(DQ_OP_APPROX_COUNT_DISTINCT, D1), op(DQ_OP_COMPLIANCE, D1, -1, 2),
+                                    op(DQ_OP_COMPLIANCE, D0, 0, 2)};
+    const DictRun r = dict_run(cols, dicts, kRows, ops, preds);
+    CHECK(r.rc == DQ_OK);
+    const DictPlan& p = r.plan;
+    // two ops on (dictionary 0, no where) share a slot with their flags OR-ed; the same dictionary under two filters: two more
+    CHECK(p.slots.size() == 4);
+    CHECK(p.opmap[0].slot == 0 && p.opmap[1].slot == 0 && p.slots[0].flags == (SF_LEN | SF_DTYPE));
+    CHECK(p.opmap[2].slot == 1 && p.opmap[3].slot == 2 && p.opmap[6].slot == 1);
+    CHECK(p.slots[1].dict == 0 && p.slots[1].where == 0 && p.slots[1].flags == 0);
+    CHECK(p.slots[2].dict == 0 && p.slots[2].where == 1 && p.slots[2].flags == SF_LEN);
+    CHECK(p.slots[3].dict == 1 && p.slots[3].where == -1 && p.slots[3].flags == SF_HLL && p.slots[3].n_dict == 1000);
+    for (size_t i = 0; i < ops.size(); ++i) {
+        const DictOpMap& m = p.opmap[i];
+        CHECK(m.op == (int)i && m.kind == ops[i].kind && m.has_where == (ops[i].where >= 0) && m.sums == nullptr);
+    }
+    CHECK(p.where_used[0] && p.where_used[1] && !p.where_used[2]);
+    // a Compliance op: a predicate op whose program copy reads column 0, the caller's program untouched
+    CHECK(p.pops.size() == 2 && p.op_pop[5] == 0 && p.op_pop[6] == 1 && p.op_pop[0] == -1);
+    CHECK(p.pops[0].pred == 2 && p.pops[0].slot == 3 && p.pops[1].pred == 2 && p.pops[1].slot == 1);
+    for (const DictPlanPred& pop : p.pops) {
+        CHECK(pop.code.size() == callers_code.size());
+        for (size_t k = 0; k + 1 < pop.code.size(); k += 2)
+            CHECK(pop.code[k] == callers_code[k] && pop.code[k + 1] == (pop.code[k] == DQ_P_COL ? 0 : callers_code[k + 1]));
+    }
+    CHECK(preds[2].code == callers_code && callers_code[1] == D1);
+    std::vector<dq_predicate> pv;
+    for (const Pred& q : preds) pv.push_back(q.view());
+    const dq_predicate rewritten = dict_pop_predicate(p, 1, pv.data());
+    CHECK(rewritten.code == p.pops[1].code.data() && rewritten.code_len == pv[2].code_len && rewritten.consts == pv[2].consts);
+    CHECK(p.max_entries == 1000 && p.nstatus == 3 + 2);
+    CHECK(p.slots[0].lds_copies == 8 && p.slots[3].lds_copies == 8 && p.lds_words == 8000);
+    // the zero block: every slot's four ranges and the sums are disjoint and tile [0, zwords)
+    std::vector<std::pair<size_t, size_t>> ranges = {{p.sums_off, 2 * p.pops.size()}};
+    for (const DictPlanSlot& s : p.slots) {
+        ranges.push_back({s.stats, (size_t)DS_COUNT});
+        ranges.push_back({s.fold, (size_t)DF_COUNT});
+        ranges.push_back({s.counts, (size_t)s.n_dict});
+        ranges.push_back({s.hll, (size_t)kHllRegs * 4 / 8});
+    }
+    std::sort(ranges.begin(), ranges.end());
+    size_t at = 0;
+    for (const auto& rg : ranges) {
+        CHECK(rg.first == at);
+        at += rg.second;
+    }
+    CHECK(at == p.zwords);
+    // staging: no smaller than every upload and read-back of the call, each 16-byte aligned, summed independently
+    const size_t nslots = p.slots.size(), npops = p.pops.size(), nops = ops.size();
+    size_t need = up16(sizeof(PredColumn) * (cols.size() + npops)) + program_staging(preds[0]) + program_staging(preds[1]) +
+                  up16(sizeof(DictSlot) * nslots) + 2 * program_staging(preds[2]) + up16(sizeof(DictPredOp) * npops) +
+                  up16(sizeof(DictOpMap) * nops) + up16(sizeof(dq_state) * nops) + up16(sizeof(int32_t) * p.nstatus) +
+                  up16(sizeof(int64_t) * DS_COUNT * nslots);
+    CHECK(p.pinned_bytes >= need);
+    CHECK(p.pinned_bytes <= need + 64);  // and sized from them, not from a slack
+    // no predicate op: the sums still get their two words, the status words their slot
+    const DictRun n = dict_run(cols, dicts, kRows, {op(DQ_OP_COMPLETENESS, D0)}, {});
+    CHECK(n.rc == DQ_OK && n.plan.pops.empty() && n.plan.zwords == n.plan.sums_off + 2 && n.plan.nstatus == 2);
+}
+
+static void case20_dict_refusals() {
+    const std::vector<dq_column> cols = table(kRows);
+    const std::vector<dq_dict_column> one = {dict_column(64, kRows)};
+    const int D0 = NCOLS;
+    expect_dict_reject(dict_run(cols, one, kRows, {op(DQ_OP_COMPLETENESS, K)}, {}), DQ_ERR_INVALID_ARGUMENT,
+                       "op 0: column 0 names no dictionary column");
+    expect_dict_reject(dict_run(cols, one, kRows, {op(DQ_OP_COMPLETENESS, D0 + 1)}, {}), DQ_ERR_INVALID_ARGUMENT,
+                       "op 0: column 10 names no dictionary column");
+    const std::string mean = "op 0: kind " + std::to_string((int)DQ_OP_MEAN) + " is not answered from a dictionary column";
+    expect_dict_reject(dict_run(cols, one, kRows, {op(DQ_OP_MEAN, D0)}, {}), DQ_ERR_UNSUPPORTED, mean.c_str());
+    expect_dict_reject(dict_run(cols, one, kRows, {op(DQ_OP_COMPLIANCE, D0)}, {}), DQ_ERR_INVALID_ARGUMENT,
+                       "op 0: Compliance needs a predicate");
+    expect_dict_reject(dict_run(cols, one, kRows, {op(DQ_OP_COMPLETENESS, D0, 1)}, {compare(K, DQ_P_LT, 25)}), DQ_ERR_INVALID_ARGUMENT,
+                       "op 0: bad where index");
+    expect_dict_reject(dict_run(cols, one, kRows, {op(DQ_OP_COMPLETENESS, D0, 0)}, {entry_equals(D0)}), DQ_ERR_UNSUPPORTED,
+                       "op 0: its where reads a dictionary column");
+    const char* plain = "dq_dict_scan: column 0 of a where must be a device column of the batch's rows";
+    std::vector<dq_column> bad = cols;
+    bad[K] = host_column(DQ_TYPE_LONG, true, kRows);
+    expect_dict_reject(dict_run(bad, one, kRows, {op(DQ_OP_COMPLETENESS, D0, 0)}, {compare(K, DQ_P_LT, 25)}), DQ_ERR_UNSUPPORTED, plain);
+    bad = cols;
+    bad[S].flags |= DQ_COL_OFFSETS64;
+    Pred s_null;
+    s_null.code = {DQ_P_COL, S, DQ_P_IS_NULL, 0};
+    expect_dict_reject(dict_run(bad, one, kRows, {op(DQ_OP_COMPLETENESS, D0, 0)}, {s_null}), DQ_ERR_UNSUPPORTED,
+                       "dq_dict_scan: column 7 of a where must be a device column of the batch's rows");
+    expect_dict_reject(dict_run(cols, one, kRows, {op(DQ_OP_COMPLETENESS, D0, 0)}, {compare(W, DQ_P_LT, 25)}), DQ_ERR_UNSUPPORTED,
+                       "dq_dict_scan: column 8 of a where must be a device column of the batch's rows");
+    bad = cols;
+    bad[K].length = 5;
+    expect_dict_reject(dict_run(bad, one, kRows, {op(DQ_OP_COMPLETENESS, D0, 0)}, {compare(K, DQ_P_LT, 25)}), DQ_ERR_UNSUPPORTED, plain);
+    Pred broken = compare(K, DQ_P_LT, 25);
+    broken.code[3] = 1;
+    expect_dict_reject(dict_run(cols, one, kRows, {op(DQ_OP_COMPLETENESS, D0, 0)}, {broken}), DQ_ERR_PREDICATE,
+                       "dq_dict_scan: predicate 0: bad constant");
+    expect_dict_reject(dict_run(cols, one, kRows, {op(DQ_OP_COMPLIANCE, D0, -1, 0)}, {broken}), DQ_ERR_PREDICATE,
+                       "dq_dict_scan: predicate 0: bad constant");
+    // one slot per dictionary column: kMaxSlots pass, one more does not
+    std::vector<dq_dict_column> many(kMaxSlots + 1, dict_column(4, kRows));
+    std::vector<dq_op> many_ops;
+    for (int d = 0; d <= kMaxSlots; ++d) many_ops.push_back(op(DQ_OP_COMPLETENESS, NCOLS + d));
+    expect_dict_reject(dict_run(cols, many, kRows, many_ops, {}), DQ_ERR_UNSUPPORTED, "dq_dict_scan: more than 256 slots");
+    many_ops.pop_back();
+    CHECK(dict_run(cols, many, kRows, many_ops, {}).rc == DQ_OK);
+    // check_dict_column, case by case
+    const std::vector<dq_op> ops = {op(DQ_OP_COMPLETENESS, D0)};
+    auto reject = [&](const dq_dict_column& d, int code, const char* text) { expect_dict_reject(dict_run(cols, {d}, kRows, ops, {}), code, text); };
+    const char* device = "dictionary column 0: device buffers with int32 offsets only";
+    const char* shape = "dictionary column 0: the dictionary is a STRING column of n_dict + 1 entries (the last one NULL) "
+                        "with offsets, a validity bitmap and bytes";
+    const char* align = "dictionary column 0: misaligned buffer";
+    dq_dict_column d = dict_column(64, kRows);
+    d.flags = 0;
+    reject(d, DQ_ERR_UNSUPPORTED, device);
+    d = dict_column(64, kRows);
+    d.dictionary.flags = 0;
+    reject(d, DQ_ERR_UNSUPPORTED, device);
+    d = dict_column(64, kRows);
+    d.dictionary.flags |= DQ_COL_OFFSETS64;
+    reject(d, DQ_ERR_UNSUPPORTED, device);
+    d = dict_column(64, 5);
+    reject(d, DQ_ERR_INVALID_ARGUMENT, "dictionary column 0 has 5 rows, batch has 50001");
+    d = dict_column(64, kRows);
+    d.indices = nullptr;
+    reject(d, DQ_ERR_INVALID_ARGUMENT, "dictionary column 0 has 50001 rows, batch has 50001");
+    d = dict_column(64, kRows);
+    d.dictionary.spark_type = DQ_TYPE_LONG;
+    reject(d, DQ_ERR_INVALID_ARGUMENT, shape);
+    d = dict_column(64, kRows);
+    d.dictionary.length = 0;
+    reject(d, DQ_ERR_INVALID_ARGUMENT, shape);
+    d.dictionary.length = INT32_MAX;
+    reject(d, DQ_ERR_INVALID_ARGUMENT, shape);
+    d = dict_column(64, kRows);
+    d.dictionary.offsets = nullptr;
+    reject(d, DQ_ERR_INVALID_ARGUMENT, shape);
+    d = dict_column(64, kRows);
+    d.dictionary.validity = nullptr;
+    reject(d, DQ_ERR_INVALID_ARGUMENT, shape);
+    d = dict_column(64, kRows);
+    d.dictionary.values = nullptr;
+    reject(d, DQ_ERR_INVALID_ARGUMENT, shape);
+    d = dict_column(64, kRows);
+    d.indices = (const int32_t*)(g_present + 2);
+    reject(d, DQ_ERR_ALIGNMENT, align);
+    d = dict_column(64, kRows);
+    d.validity = (const uint8_t*)g_present + 4;
+    reject(d, DQ_ERR_ALIGNMENT, align);
+    d = dict_column(64, kRows);
+    d.dictionary.values = g_present + 2;
+    reject(d, DQ_ERR_ALIGNMENT, align);
+    d = dict_column(64, kRows);
+    d.dictionary.offsets = (const int32_t*)(g_present + 2);
+    reject(d, DQ_ERR_ALIGNMENT, align);
+    d = dict_column(64, kRows);
+    d.dictionary.validity = (const uint8_t*)g_present + 4;
+    reject(d, DQ_ERR_ALIGNMENT, align);
+    d = dict_column(64, kRows);
+    d.validity = nullptr;  // all rows valid
+    CHECK(dict_run(cols, {d}, kRows, ops, {}).rc == DQ_OK);
+    std::string msg;
+    CHECK(check_dict_column(dict_column(1, 0), 0, 0, &msg) == DQ_OK && msg.empty());
+}
+
+static void case21_dict_lds_copies() {
+    const DictOptions dflt;
+    CHECK(dflt.lds_entries == kDictLdsWords && dflt.lds_copies == kDictLdsCopies);
+    CHECK(dict_lds_copies(dflt, 0, kRows, 64) == 0);
+    CHECK(dict_lds_copies(dflt, 10, kRows, 64) == 8);
+    DictOptions o;
+    o.lds_entries = 100;
+    CHECK(dict_lds_copies(o, 100, kRows, 64) == 8 && dict_lds_copies(o, 101, kRows, 64) == 0);
+    o.lds_entries = 0;
+    CHECK(dict_lds_copies(o, 1, kRows, 64) == 0);
+    o.lds_entries = 1 << 20;  // never more than the LDS holds
+    CHECK(dict_lds_copies(o, kDictLdsWords, kRows, 64) == 1 && dict_lds_copies(o, kDictLdsWords + 1, kRows, 64) == 0);
+    // copies halve until they fit kDictLdsCopyWords = 8192 words
+    CHECK(dict_lds_copies(dflt, 1024, kRows, 64) == 8 && dict_lds_copies(dflt, 1025, kRows, 64) == 4);
+    CHECK(dict_lds_copies(dflt, 2048, kRows, 64) == 4 && dict_lds_copies(dflt, 2049, kRows, 64) == 2);
+    CHECK(dict_lds_copies(dflt, 4097, kRows, 64) == 1 && dict_lds_copies(dflt, kDictLdsWords, kRows, 64) == 1);
+    CHECK(dict_lds_copies(dflt, kDictLdsWords + 1, kRows, 64) == 0);
+    // a workgroup's rows, nrows / grid + 2 tiles, stay below 2^31
+    const int64_t cut = ((int64_t)1 << 31) - 2 * kDictTileRows;
+    CHECK(dict_lds_copies(dflt, 10, cut - 1, 1) == 8 && dict_lds_copies(dflt, 10, cut, 1) == 0);
+    CHECK(dict_lds_copies(dflt, 10, 64 * cut - 1, 64) == 8 && dict_lds_copies(dflt, 10, 64 * cut, 64) == 0);
+    for (int c : {1, 2, 4}) {
+        o = DictOptions();
+        o.lds_copies = c;
+        CHECK(dict_lds_copies(o, 10, kRows, 64) == c);
+        CHECK(dict_lds_copies(o, 4097, kRows, 64) == 1);
+    }
+    for (int c : {3, 0, -1, 16}) {  // ignored
+        o = DictOptions();
+        o.lds_copies = c;
+        CHECK(dict_lds_copies(o, 10, kRows, 64) == 8);
+    }
+}
+
 int main() {
     case1_heavy2();
     case2_fused_producer();
@@ -628,6 +1079,13 @@ int main() {
     case13_geometry();
     case14_rejected_examples();
     case14_random_programs();
+    case15_row_term_order();
+    case16_row_inline();
+    case17_row_sources();
+    case18_row_refusals();
+    case19_dict_plan();
+    case20_dict_refusals();
+    case21_dict_lds_copies();
     if (g_failed) {
         printf("scan_plan_checks: %d FAILED\n", g_failed);
         return 1;
