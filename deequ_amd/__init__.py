@@ -17,9 +17,15 @@ from .analyzers import (Size, Completeness, Compliance, Mean, Sum, Minimum, Maxi
                         MutualInformation, Histogram, FrequenciesAndNumRows, Preconditions, computeFrequencies)
 from .kll import (KLLParameters, KLLState, KLLMetric, BucketDistribution, BucketValue, QuantileNonSample)
 from .runners import (AnalysisRunner, KLLRunner, AnalysisRunBuilder, AnalyzerContext, Analysis, InMemoryStateProvider,
-                      ScanBatch)
+                      ScanBatch, ReusingNotPossibleResultsMissingException)
 from .checks import (Check, CheckLevel, CheckStatus, ConstraintStatus, ConstrainableDataTypes, VerificationSuite,
-                     VerificationResult)
+                     VerificationResult, VerificationRunBuilder, AnomalyCheckConfig)
+from .repository import (ResultKey, AnalysisResult, AnalysisResultSerde, MetricsRepository,
+                         MetricsRepositoryMultipleResultsLoader, InMemoryMetricsRepository,
+                         FileSystemMetricsRepository)
+from .anomaly import (DataPoint, Anomaly, DetectionResult, AnomalyDetector, AnomalyDetectionStrategy,
+                      SimpleThresholdStrategy, AbsoluteChangeStrategy, RateOfChangeStrategy,
+                      RelativeRateOfChangeStrategy, BatchNormalStrategy, OnlineNormalStrategy, HoltWinters)
 from .rowlevel import RowLevelResults
 from .table import ChunkedTable, Table, Column
 from .profiles import (ColumnProfiler, ColumnProfilerRunner, ColumnProfilerRunBuilder, ColumnProfiles,

@@ -5,13 +5,16 @@ required analyzers and hands them to ONE AnalysisRunner.doAnalysisRun (so all sc
 metrics of all checks come from one fused dq_scan), then evaluates the assertions on the metrics.
 VerificationResult.rowLevelResultsAsTable adds one pass / fail column per check to the data (rowlevel.py: the
 per-row outcomes are computed and kept on the GPU).
-Anomaly detection, KLL sketches, metrics repositories and file output are out of scope.
+A run may name a MetricsRepository (repository.py): metrics it holds are reused, the run's are saved after the checks
+are evaluated, and an anomaly check (anomaly.py) judges a new metric against the history saved there.
+KLL constraints are out of scope.
 """
 import enum
+import json
 
 from . import analyzers as A
 from .analyzers import _java_double_to_string
-from .runners import AnalysisRunner, AnalyzerContext
+from .runners import AnalysisRunner, AnalyzerContext, RepositoryOptions
 
 
 class CheckLevel(enum.Enum):
@@ -133,7 +136,7 @@ class CheckResult:
 
 
 class Check:
-    """M/checks/Check.scala:60-1056 (anomaly and KLL constraints excluded)."""
+    """M/checks/Check.scala:60-1056 (KLL constraints excluded)."""
 
     def __init__(self, level, description, constraints=None):
         self.level, self.description = level, description
@@ -206,6 +209,41 @@ class Check:
                            maxBins=A.Histogram.MaximumAllowedDetailBins, hint=None):
         h = A.Histogram(column, binningUdf, maxBins)
         return self.addConstraint(_named(h, assertion, "HistogramConstraint(%r)" % h, hint=hint))
+
+    # ---- anomaly detection ------------------------------------------------------------------
+    def isNewestPointNonAnomalous(self, metricsRepository, anomalyDetectionStrategy, analyzer, withTagValues=None,
+                                  afterDate=None, beforeDate=None, hint=None):
+        """M/checks/Check.scala:345-365: the analyzer's new value is no anomaly against its history in the repository
+        (the results under `withTagValues`, from `afterDate` to `beforeDate`, both inclusive)."""
+        def assertion(currentMetricValue):
+            return Check.isNewestPointNonAnomalousAssertion(metricsRepository, anomalyDetectionStrategy, analyzer,
+                                                            withTagValues or {}, afterDate, beforeDate,
+                                                            currentMetricValue)
+        return self.addConstraint(_named(analyzer, assertion, "AnomalyConstraint(%r)" % analyzer, hint=hint))
+
+    @staticmethod
+    def isNewestPointNonAnomalousAssertion(metricsRepository, anomalyDetectionStrategy, analyzer, withTagValues,
+                                           afterDate, beforeDate, currentMetricValue):
+        """Check.isNewestPointNonAnomalous of the companion object (M/checks/Check.scala:998-1055)."""
+        from .anomaly import AnomalyDetector, DataPoint, LONG_MAX, extractMetricValues, require
+        loader = metricsRepository.load().withTagValues(withTagValues)
+        if beforeDate is not None:
+            loader = loader.before(beforeDate)
+        if afterDate is not None:
+            loader = loader.after(afterDate)
+        analysisResults = loader.forAnalyzers([analyzer]).get()
+        require(len(analysisResults) > 0, "There have to be previous results in the MetricsRepository!")
+        # two results of one date are unusual: sorted by their tag values first (a stable sort), they come out of the
+        # detector's sort by time in one order whatever the store returned
+        ordered = sorted(analysisResults, key=lambda r: list(r.resultKey.tags.values()))
+        historicalMetrics = [(r.resultKey.dataSetDate, next(iter(r.analyzerContext.metricMap.values()), None))
+                             for r in ordered]
+        testDateTime = max(r.resultKey.dataSetDate for r in analysisResults) + 1
+        require(testDateTime != LONG_MAX, "Test DateTime cannot be Long.MaxValue, otherwise theAnomaly Detection, "
+                "which works with an open upper interval bound, won't test anything")
+        detected = AnomalyDetector(anomalyDetectionStrategy).isNewPointAnomalous(
+            extractMetricValues(historicalMetrics), DataPoint(testDateTime, currentMetricValue))
+        return not detected.anomalies
 
     # ---- information ------------------------------------------------------------------------
     def hasEntropy(self, column, assertion, hint=None):
@@ -384,6 +422,17 @@ class VerificationResult:
         return AnalyzerContext.successMetricsAsJson(AnalyzerContext(result.metrics), forAnalyzers)
 
     @staticmethod
+    def checkResultsAsJson(result, forChecks=()):
+        """M/VerificationResult.scala:73-115: one row per constraint result (`forChecks` is unused there too)."""
+        rows = []
+        for r in result.checkResults.values():
+            for c in r.constraintResults:
+                rows.append({"check": r.check.description, "check_level": r.check.level.value,
+                             "check_status": r.status.name, "constraint": str(c.constraint),
+                             "constraint_status": c.status.value, "constraint_message": c.message or ""})
+        return json.dumps(rows)
+
+    @staticmethod
     def rowLevelResultsAsTable(result, data, filteredRow="true", strict=False):
         """rowLevelResultsAsDataFrame of later deequ releases: `data` plus one BOOLEAN column per check of `result`
         that has a row-level constraint, named by the check's description; row i is the AND of those constraints'
@@ -404,6 +453,53 @@ class VerificationRunBuilder:
         self.requiredAnalyzers = []
         self._aggregateWith = None
         self._saveStatesWith = None
+        self._repository = RepositoryOptions()
+        self._check_results_path = None
+        self._success_metrics_path = None
+        self._overwrite = False
+
+    def useRepository(self, metricsRepository):
+        """The MetricsRepository (repository.py) of reuseExistingResultsForKey, saveOrAppendResult and
+        addAnomalyCheck."""
+        self._repository.metricsRepository = metricsRepository
+        return self
+
+    def reuseExistingResultsForKey(self, resultKey, failIfResultsMissing=False):
+        self._repository.need_repository("reuseExistingResultsForKey")
+        self._repository.reuseExistingResultsForKey = resultKey
+        self._repository.failIfResultsForReusingMissing = bool(failIfResultsMissing)
+        return self
+
+    def saveOrAppendResult(self, resultKey):
+        """The run's metrics are added to what the repository holds under `resultKey`, after the checks (an anomaly
+        check sees the history without the run it judges)."""
+        self._repository.need_repository("saveOrAppendResult")
+        self._repository.saveOrAppendResultsWithKey = resultKey
+        return self
+
+    def addAnomalyCheck(self, anomalyDetectionStrategy, analyzer, anomalyCheckConfig=None):
+        """M/VerificationRunBuilder.scala:227-243: a check that the analyzer's metric of this run is no anomaly
+        against its history in the repository."""
+        self._repository.need_repository("addAnomalyCheck")
+        config = anomalyCheckConfig
+        if config is None:
+            config = AnomalyCheckConfig(CheckLevel.Warning, "Anomaly check for %r" % (analyzer,))
+        self.checks.append(Check(config.level, config.description).isNewestPointNonAnomalous(
+            self._repository.metricsRepository, anomalyDetectionStrategy, analyzer, config.withTagValues,
+            config.afterDate, config.beforeDate))
+        return self
+
+    def saveCheckResultsJsonToPath(self, path):
+        self._check_results_path = path
+        return self
+
+    def saveSuccessMetricsJsonToPath(self, path):
+        self._success_metrics_path = path
+        return self
+
+    def overwritePreviousFiles(self, flag):
+        self._overwrite = bool(flag)
+        return self
 
     def addCheck(self, check):
         self.checks.append(check)
@@ -430,8 +526,20 @@ class VerificationRunBuilder:
         return self
 
     def run(self):
-        return VerificationSuite.doVerificationRun(self.data, self.checks, self.requiredAnalyzers,
-                                                   self._aggregateWith, self._saveStatesWith)
+        return VerificationSuite.doVerificationRun(
+            self.data, self.checks, self.requiredAnalyzers, self._aggregateWith, self._saveStatesWith,
+            saveCheckResultsJsonToPath=self._check_results_path,
+            saveSuccessMetricsJsonToPath=self._success_metrics_path, overwriteOutputFiles=self._overwrite,
+            **self._repository.arguments())
+
+
+class AnomalyCheckConfig:
+    """M/VerificationRunBuilder.scala:336-341."""
+
+    def __init__(self, level, description, withTagValues=None, afterDate=None, beforeDate=None):
+        self.level, self.description = level, description
+        self.withTagValues = dict(withTagValues or {})
+        self.afterDate, self.beforeDate = afterDate, beforeDate
 
 
 class VerificationSuite:
@@ -441,11 +549,34 @@ class VerificationSuite:
         return VerificationRunBuilder(data)
 
     @staticmethod
-    def doVerificationRun(data, checks, requiredAnalyzers=(), aggregateWith=None, saveStatesWith=None):
-        """M/VerificationSuite.scala:107-144: one analysis run for every check's analyzers."""
+    def doVerificationRun(data, checks, requiredAnalyzers=(), aggregateWith=None, saveStatesWith=None,
+                          metricsRepository=None, reuseExistingResultsForKey=None,
+                          failIfResultsForReusingMissing=False, saveOrAppendResultsWithKey=None,
+                          saveCheckResultsJsonToPath=None, saveSuccessMetricsJsonToPath=None,
+                          overwriteOutputFiles=False):
+        """M/VerificationSuite.scala:107-144: one analysis run for every check's analyzers. The run's metrics go to
+        the repository after the checks are evaluated (:121-139), so that an anomaly check reads the history
+        without the point it judges. The JSON outputs take local paths."""
         analyzers = list(requiredAnalyzers) + [a for c in checks for a in c.requiredAnalyzers()]
-        context = AnalysisRunner.doAnalysisRun(data, analyzers, aggregateWith, saveStatesWith)
-        return VerificationSuite.evaluate(checks, context)
+        if metricsRepository is None:
+            context = AnalysisRunner.doAnalysisRun(data, analyzers, aggregateWith, saveStatesWith)
+        else:
+            context = AnalysisRunner.doAnalysisRun(data, analyzers, aggregateWith, saveStatesWith,
+                                                   metricsRepository=metricsRepository,
+                                                   reuseExistingResultsForKey=reuseExistingResultsForKey,
+                                                   failIfResultsForReusingMissing=failIfResultsForReusingMissing)
+        result = VerificationSuite.evaluate(checks, context)
+        AnalysisRunner.saveOrAppendResultsIfNecessary(AnalyzerContext(result.metrics), metricsRepository,
+                                                      saveOrAppendResultsWithKey)
+        if saveCheckResultsJsonToPath is not None or saveSuccessMetricsJsonToPath is not None:
+            from .suggestions import _write_text
+            if saveCheckResultsJsonToPath is not None:
+                _write_text(saveCheckResultsJsonToPath, VerificationResult.checkResultsAsJson(result),
+                            overwriteOutputFiles, False, "CHECK RESULTS")
+            if saveSuccessMetricsJsonToPath is not None:
+                _write_text(saveSuccessMetricsJsonToPath, VerificationResult.successMetricsAsJson(result),
+                            overwriteOutputFiles, False, "SUCCESS METRICS")
+        return result
 
     @staticmethod
     def evaluate(checks, context):

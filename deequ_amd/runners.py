@@ -365,6 +365,12 @@ class AnalyzerContext:
         m.update(other.metricMap)
         return AnalyzerContext(m)
 
+    def __eq__(self, other):  # the reference's case class: equal metric maps
+        return isinstance(other, AnalyzerContext) and self.metricMap == other.metricMap
+
+    def __hash__(self):
+        return hash(frozenset(self.metricMap))
+
     @staticmethod
     def successMetricsAsJson(analyzerContext, forAnalyzers=()):
         rows = []
@@ -408,6 +414,30 @@ class Analysis:
         return AnalysisRunner.doAnalysisRun(data, self.analyzers, aggregateWith, saveStatesWith)
 
 
+class ReusingNotPossibleResultsMissingException(RuntimeError):
+    """R/AnalysisRunner.scala:130-134: `failIfResultsMissing` and the repository lacks a metric the run needs."""
+
+
+class RepositoryOptions:
+    """AnalysisRunnerRepositoryOptions (R/AnalysisRunner.scala) as the run builders collect it."""
+
+    def __init__(self):
+        self.metricsRepository = None
+        self.reuseExistingResultsForKey = None
+        self.failIfResultsForReusingMissing = False
+        self.saveOrAppendResultsWithKey = None
+
+    def need_repository(self, what):
+        if self.metricsRepository is None:  # the reference has these methods on the builder useRepository returns
+            raise ValueError("%s needs a repository: call useRepository(...) first" % what)
+
+    def arguments(self):
+        return dict(metricsRepository=self.metricsRepository,
+                    reuseExistingResultsForKey=self.reuseExistingResultsForKey,
+                    failIfResultsForReusingMissing=self.failIfResultsForReusingMissing,
+                    saveOrAppendResultsWithKey=self.saveOrAppendResultsWithKey)
+
+
 class AnalysisRunBuilder:
     """R/AnalysisRunBuilder.scala:27-116."""
 
@@ -416,6 +446,25 @@ class AnalysisRunBuilder:
         self.analyzers = []
         self._aggregateWith = None
         self._saveStatesWith = None
+        self._repository = RepositoryOptions()
+
+    def useRepository(self, metricsRepository):
+        """The MetricsRepository (repository.py) of reuseExistingResultsForKey and saveOrAppendResult."""
+        self._repository.metricsRepository = metricsRepository
+        return self
+
+    def reuseExistingResultsForKey(self, resultKey, failIfResultsMissing=False):
+        """Metrics the repository holds under `resultKey` are taken from there; only the other analyzers run."""
+        self._repository.need_repository("reuseExistingResultsForKey")
+        self._repository.reuseExistingResultsForKey = resultKey
+        self._repository.failIfResultsForReusingMissing = bool(failIfResultsMissing)
+        return self
+
+    def saveOrAppendResult(self, resultKey):
+        """The run's metrics are added to what the repository holds under `resultKey` (this run's win)."""
+        self._repository.need_repository("saveOrAppendResult")
+        self._repository.saveOrAppendResultsWithKey = resultKey
+        return self
 
     def addAnalyzer(self, analyzer):
         self.analyzers.append(analyzer)
@@ -434,7 +483,10 @@ class AnalysisRunBuilder:
         return self
 
     def run(self):
-        return AnalysisRunner.doAnalysisRun(self.data, self.analyzers, self._aggregateWith, self._saveStatesWith)
+        if self._repository.metricsRepository is None:  # the call of a run that names no repository, as it was
+            return AnalysisRunner.doAnalysisRun(self.data, self.analyzers, self._aggregateWith, self._saveStatesWith)
+        return AnalysisRunner.doAnalysisRun(self.data, self.analyzers, self._aggregateWith, self._saveStatesWith,
+                                            **self._repository.arguments())
 
     def runAsync(self, priority=0):
         """run() on a helper context of this thread's device (own stream and scratch) in a helper thread, beside the
@@ -541,8 +593,40 @@ class AnalysisRunner:
         return AnalysisRunner.doAnalysisRun(data, analysis.analyzers, aggregateWith, saveStatesWith)
 
     @staticmethod
-    def doAnalysisRun(data, analyzers, aggregateWith=None, saveStatesWith=None):
-        """R/AnalysisRunner.scala:97-203 (repository reuse and file output are out of scope)."""
+    def doAnalysisRun(data, analyzers, aggregateWith=None, saveStatesWith=None, metricsRepository=None,
+                      reuseExistingResultsForKey=None, failIfResultsForReusingMissing=False,
+                      saveOrAppendResultsWithKey=None):
+        """R/AnalysisRunner.scala:97-203. With a `metricsRepository` (repository.py): the metrics it holds under
+        `reuseExistingResultsForKey` are not computed again (:115-134), and the result -- those metrics ++ this
+        run's -- is added to what it holds under `saveOrAppendResultsWithKey` (:205-223). The run of the analyzers
+        that are left is the same for a Table and a ChunkedTable, on this thread or under runAsync."""
+        if not analyzers:
+            return AnalyzerContext.empty()
+        if metricsRepository is None:
+            return AnalysisRunner._computeMetrics(data, analyzers, aggregateWith, saveStatesWith)
+        previous = AnalyzerContext.empty()
+        if reuseExistingResultsForKey is not None:
+            previous = metricsRepository.loadByKey(reuseExistingResultsForKey) or previous
+        toRun = [a for a in analyzers if a not in previous.metricMap]
+        if failIfResultsForReusingMissing and toRun:
+            raise ReusingNotPossibleResultsMissingException(
+                "Could not find all necessary results in the MetricsRepository, the calculation of the metrics for "
+                "these analyzers would be needed: %s" % ", ".join(repr(a) for a in toRun))
+        result = previous + AnalysisRunner._computeMetrics(data, toRun, aggregateWith, saveStatesWith)
+        AnalysisRunner.saveOrAppendResultsIfNecessary(result, metricsRepository, saveOrAppendResultsWithKey)
+        return result
+
+    @staticmethod
+    def saveOrAppendResultsIfNecessary(resultingAnalyzerContext, metricsRepository, saveOrAppendResultsWithKey):
+        """R/AnalysisRunner.scala:205-223: what the key already holds ++ the new result (the right-hand side wins)."""
+        if metricsRepository is None or saveOrAppendResultsWithKey is None:
+            return
+        current = metricsRepository.loadByKey(saveOrAppendResultsWithKey) or AnalyzerContext.empty()
+        metricsRepository.save(saveOrAppendResultsWithKey, current + resultingAnalyzerContext)
+
+    @staticmethod
+    def _computeMetrics(data, analyzers, aggregateWith=None, saveStatesWith=None):
+        """The metrics of `analyzers` over `data` (R/AnalysisRunner.scala:136-193)."""
         if not analyzers:
             return AnalyzerContext.empty()
         if isinstance(data, ChunkedTable):
